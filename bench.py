@@ -19,6 +19,12 @@ Other configurations, for DESIGN.md / profiles -- the driver's 
   --host-stream   the batch starts in pinned host memory: H2D copy of batch k+1 overlaps the
                   processing of batch k (PCIe-inclusive rate; never the headline value)
 
+A run without --full does what the headline figure needs: set-up, warm-up, the timed steps, the
+line.  --full adds the parity check against the oracle, socket power (during the timed steps and in
+untimed holds after them), the isolated per-stage split, the VALU-issue calibration and the CPU
+baseline; without it their places in the line are null.  --dump-outputs DIR writes the blobs of the
+last timed batch as .npy files (dump_outputs), for comparing two builds output for output.
+
 Prints one JSON line (rank 0).  Extra diagnostics go to stderr.
 """
 import argparse
@@ -125,6 +131,14 @@ def main():
     ap.add_argument("--steps", type=int, default=None,
                     help="timed steps (default: about 3 s of work for the workload)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the parity check against the oracle, socket power "
+                         "during the timed steps and the untimed power holds, the isolated per-stage split, the "
+                         "VALU-issue calibration and the CPU baseline (a run without --full sets up, warms up, "
+                         "times the steps and prints the line, with null where these would stand)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the blobs bw_wait returned for the last timed batch to "
+                         "DIR/<field>.npy (see dump_outputs)")
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c4", "c5"])
     ap.add_argument("--gib", type=float, default=None,
                     help="C2: stream size per GPU; C1: corpus size; C3/C5: base image size (GiB)")
@@ -194,9 +208,14 @@ def main():
     if args.gpus is not None and args.gpus != world_env:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: refusing to report a %d-GPU line" %
                          (args.gpus, world_env, world_env))
+    if not args.full:
+        # the plain run measures the headline figure only; what else the line can carry is --full's
+        args.no_check = args.no_power = args.no_holds = args.no_calibrate = args.no_cpu_baseline = True
     if args.dry_run:
         return dry_run(args)
     if args.split_files:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs covers the batch path (bw_wait's blobs), not --split-files")
         return split_files_bench(args)
     if args.steps is None:
         args.steps = {"c1": 3000, "c2": 320, "c3": 80, "c4": 200, "c5": 5}[args.workload]
@@ -405,6 +424,7 @@ def main():
     if multi:
         dist.barrier()
     el = time.perf_counter() - t0
+    last_res = out_buf[:n_out.value].copy()  # the last timed batch's blobs, as bw_wait handed them over
     power, power_missing = sampler.stop() if sampler else (None, None)
     if multi:
         t = torch.tensor([el], dtype=torch.float64, device="cpu" if host_tp else dev)
@@ -429,7 +449,7 @@ def main():
         leaf_union += cur[1] - cur[0]
     leaf_active_ms = leaf_union / args.steps if leaf_iv else None
     iso = None
-    if not multi and host is None:
+    if args.full and not multi and host is None:
         # the same batch with nothing beside it (one context, synchronized, every stage marked):
         # each kernel's own duration, reported next to the live one, which shares the GPU with
         # the other batches in flight (and has only the roofline's kernels marked)
@@ -538,7 +558,8 @@ def main():
                                              {dom: round(per[dom], 3)}),
                 "marked_stage_note": ("every stage marked (--all-stage-marks)" if args.all_stage_marks else
                                       "only the leaf pass is marked in the timed region (each mark costs ~5 us); "
-                                      "the full stage split is isolated.stage_ms_per_step")}
+                                      "the full stage split is isolated.stage_ms_per_step" +
+                                      ("" if args.full else " of a --full run"))}
     valu = None
     if kernel == leaf_kernel and not args.no_calibrate:
         # the limit this kernel actually meets: integer VALU issue, measured now on this chip
@@ -591,10 +612,12 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, data, file_off, file_len)
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_res, rank, world)
     if rank == 0:
         line = {"metric": METRIC, "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-                "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+                "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic", "full": args.full,
                 "config": {"workload": desc + (" -- streamed from pinned host memory" if host is not None else "") +
                            (" -- REHEARSAL: host transport, %d ranks on %d GPU(s)" % (world, torch.cuda.device_count())
                             if host_tp and multi else ""),
@@ -620,6 +643,33 @@ def main():
         comm.close()
     if multi:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ROWS = 1 << 18  # --dump-outputs: 188 B per blob on disk, so at most 47 MiB for the whole job
+
+
+def dump_outputs(path, res, rank, world):
+    """--dump-outputs: the blobs bw_wait returned for the last timed batch (what a caller of the
+    batch path receives), one .npy per field of the record under `path`; ranks past the first prefix
+    their files with rank<r>_.  Every value is exact in the type it is stored in: file, offset,
+    length and the two 32-bit halves of the gear hash as float64, the digest's 32 bytes and the
+    duplicate verdict as float32.  A batch of more than DUMP_MAX_ROWS / world blobs (C4) is sampled:
+    a fixed seeded choice of rows in ascending order; row.npy holds the rows written either way."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = max(1, DUMP_MAX_ROWS // world)
+    rows = np.arange(len(res))
+    if len(res) > cap:
+        rows = np.sort(np.random.default_rng(0).choice(len(res), cap, replace=False))
+    res = res[rows]
+    gear = res["gear_hash"]
+    pre = "rank%d_" % rank if rank else ""
+    for name, a, dt in (("row", rows, np.float64), ("file", res["file"], np.float64),
+                        ("offset", res["offset"], np.float64), ("length", res["length"], np.float64),
+                        ("gear_hash_lo", gear & np.uint64(0xFFFFFFFF), np.float64),
+                        ("gear_hash_hi", gear >> np.uint64(32), np.float64),
+                        ("digest", res["digest"], np.float32), ("is_dup", res["is_dup"], np.float32)):
+        np.save(os.path.join(path, pre + name + ".npy"), np.ascontiguousarray(a, dtype=dt))
 
 
 def split_files_bench(args):

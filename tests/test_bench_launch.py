@@ -59,6 +59,58 @@ def test_bench_refuses_world_mismatch():
     assert "refusing" in out.stderr
 
 
+def test_dump_outputs_is_exact_and_bounded(tmp_path):
+    """--dump-outputs: every field of the blob record comes back bit for bit from the float arrays
+    (the 64-bit gear hash from its halves); a batch past the row cap is a fixed sample, within 64 MB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from backuwup_amd import BLOB_DTYPE
+    rng = np.random.default_rng(7)
+    n = 1000
+    res = np.zeros(n, dtype=BLOB_DTYPE)
+    res["file"] = np.arange(n) // 3
+    res["offset"] = rng.integers(0, 1 << 44, n, dtype=np.uint64)
+    res["length"] = rng.integers(1, 3 << 20, n, dtype=np.uint64)
+    res["gear_hash"] = rng.integers(0, 1 << 64, n, dtype=np.uint64)
+    res["gear_hash"][0] = 0xFFFFFFFFFFFFFFFF
+    res["digest"] = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    res["is_dup"] = rng.integers(0, 2, n, dtype=np.uint8)
+    d = str(tmp_path / "whole")
+    bench.dump_outputs(d, res, 0, 1)
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert sorted(got) == ["digest", "file", "gear_hash_hi", "gear_hash_lo", "is_dup", "length", "offset", "row"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["row"], np.arange(n))
+    for f in ("file", "offset", "length", "digest", "is_dup"):
+        assert np.array_equal(got[f].astype(BLOB_DTYPE[f].base), res[f]), f
+    gear = (got["gear_hash_hi"].astype(np.uint64) << np.uint64(32)) | got["gear_hash_lo"].astype(np.uint64)
+    assert np.array_equal(gear, res["gear_hash"])
+    # past the cap: the same rows on every call, ascending, and under 64 MB on disk for the whole job
+    big = np.zeros(bench.DUMP_MAX_ROWS + 5000, dtype=BLOB_DTYPE)
+    big["offset"] = np.arange(len(big))
+    sizes = []
+    for k in ("a", "b"):
+        d = str(tmp_path / k)
+        bench.dump_outputs(d, big, 0, 1)
+        sizes.append(sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)))
+    rows = np.load(str(tmp_path / "a" / "row.npy"))
+    assert len(rows) == bench.DUMP_MAX_ROWS and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(str(tmp_path / "b" / "row.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "a" / "offset.npy")), rows)
+    assert sizes[0] == sizes[1] <= 64 * 1000 * 1000
+    bench.dump_outputs(str(tmp_path / "r1"), res, 1, 2)  # a second rank's files carry its rank
+    assert "rank1_digest.npy" in os.listdir(str(tmp_path / "r1"))
+
+
+def test_bench_full_and_dump_options_parse():
+    """--full and --dump-outputs are options of the one command line (dry run: nothing to dump)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run", "--full",
+                          "--steps", "2", "--warmup", "1"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+
+
 def _a2a_worker(rank, world, port, q):
     import torch.distributed as dist
     from backuwup_amd.comm import gloo_all_to_all

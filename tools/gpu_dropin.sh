@@ -75,10 +75,10 @@ if [[ " $PARTS " == *" c4ab "* ]]; then  # round 6: the service's completers yie
   done
 fi
 if [[ " $PARTS " == *" c4cpu "* ]]; then
-  run bench_c4_cpu 900 python3 bench.py --workload c4 --steps 20 --cpu-trees || exit 1
+  run bench_c4_cpu 900 python3 bench.py --full --workload c4 --steps 20 --cpu-trees || exit 1
 fi
 if [[ " $PARTS " == *" cpu "* ]]; then
-  run bench_c1_cpu 600 python3 bench.py --workload c1 --steps 300 || exit 1
-  run bench_c4_cpu 900 python3 bench.py --workload c4 --steps 20 --cpu-trees || exit 1
+  run bench_c1_cpu 600 python3 bench.py --full --workload c1 --steps 300 || exit 1
+  run bench_c4_cpu 900 python3 bench.py --full --workload c4 --steps 20 --cpu-trees || exit 1
 fi
 exit 0

@@ -7,7 +7,7 @@
 #   collide  tools/collide.hip (BLAKE3 8-byte prefix collision -> gpurun_out/*.json)
 #   slab     tools/gpu_slab.sh (Infinity-Cache reuse of the leaf pass)
 #   dropin   tools/gpu_dropin.sh (the reference's call sites on C1)
-#   bench    python bench.py $BENCH_ARGS         prof    rocprofv3 --kernel-trace --stats of the bench
+#   bench    python bench.py ${BENCH_ARGS:---full}   prof    rocprofv3 --kernel-trace --stats of the bench
 #   pmc      tools/gpu_pmc.sh (FETCH_SIZE / WRITE_SIZE passes -> pmc_traffic.json)
 #   debug    tools/debug_check.py (BW_DEBUG + BW_DIAG library)
 #   rehearse bench.py --gpus 2 / 4 --transport host on one GPU (the N > 1 path end to end)
@@ -39,44 +39,44 @@ for s in $STEPS; do
            --timeout 240 --timeout-method thread ;;
     full) step pytest_full 600 python -u -m pytest tests/test_gpu_full_configs.py -m gpu -v -p no:cacheprovider \
            --timeout 300 --timeout-method thread ;;
-    bench20) step bench20 300 python bench.py --steps 20 --no-cpu-baseline ;;
+    bench20) step bench20 300 python bench.py --full --steps 20 --no-cpu-baseline ;;
     collide) step collide 120 ./build_ab/collide "$OUT/blake3_prefix_collision.json" 14 32768 1 ;;
     slab) step slab 900 bash tools/gpu_slab.sh ;;
     dropin) step dropin 1100 bash tools/gpu_dropin.sh ;;
-    bench) step bench 600 python bench.py ${BENCH_ARGS:-} ;;
+    bench) step bench 600 python bench.py ${BENCH_ARGS:---full} ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run \
-        --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-holds) || exit 1
+        --output-format csv -- python3 "$OLDPWD/bench.py" --full --no-cpu-baseline --no-holds) || exit 1
       T=$(find "$OUT/prof" -name "*kernel_trace.csv" | head -1)
       [ -n "$T" ] && python3 tools/trace_split.py "$T" k_b3_lines 2 320 17179869184 > "$OUT/trace_split.json" 2>&1 ;;
     pmc) step pmc 900 bash tools/gpu_pmc.sh ;;
     slabpmc) step slabpmc 600 env CONFIGS=" " bash tools/gpu_slab.sh ;;
     dropsweep) step dropsweep 600 env DROPIN_ONLY=1 bash tools/gpu_dropin.sh ;;
     configs)
-      step bench_c1_1 600 python bench.py --workload c1 --streams 1 --steps 1500 --no-cpu-baseline &&
-      step bench_c3 600 python bench.py --workload c3 --steps 40 --no-cpu-baseline &&
-      step bench_c4 600 python bench.py --workload c4 --steps 60 --no-cpu-baseline &&
-      step bench_c5 600 python bench.py --workload c5 --steps 3 --no-cpu-baseline ;;
+      step bench_c1_1 600 python bench.py --full --workload c1 --streams 1 --steps 1500 --no-cpu-baseline &&
+      step bench_c3 600 python bench.py --full --workload c3 --steps 40 --no-cpu-baseline &&
+      step bench_c4 600 python bench.py --full --workload c4 --steps 60 --no-cpu-baseline &&
+      step bench_c5 600 python bench.py --full --workload c5 --steps 3 --no-cpu-baseline ;;
     debug) step debug_check 600 python tools/debug_check.py ;;
     rehearse)  # round 6: the driver's N > 1 bench path on one GPU (host transport, ranks share the GPU)
       step bench_n2_host 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29533 bench.py --gpus 2 --transport host --steps 20 --warmup 2 --no-holds &&
+        --master-port 29533 bench.py --full --gpus 2 --transport host --steps 20 --warmup 2 --no-holds &&
       step bench_n4_host 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-        --master-port 29534 bench.py --gpus 4 --transport host --steps 10 --warmup 2 --no-holds ;;
+        --master-port 29534 bench.py --full --gpus 4 --transport host --steps 10 --warmup 2 --no-holds ;;
     attrib)  # round 5, VERDICT r4 #4: what limits the overlap of the scan and the leaf pass (build first:
              # python backuwup_amd/build.py --clock); then the bench at the driver's 20 steps, the
              # default 320 and 2,000 (18 s), each with its power and clock samples
       step clock_windows 300 python tools/clock_windows.py --steps 400 --window 24 &&
-      step bench_s20 300 python bench.py --steps 20 --no-cpu-baseline --no-calibrate &&
-      step bench_s320 300 python bench.py --steps 320 --no-cpu-baseline --no-calibrate &&
-      step bench_s2000 600 python bench.py --steps 2000 --no-cpu-baseline --no-calibrate ;;
+      step bench_s20 300 python bench.py --full --steps 20 --no-cpu-baseline --no-calibrate &&
+      step bench_s320 300 python bench.py --full --steps 320 --no-cpu-baseline --no-calibrate &&
+      step bench_s2000 600 python bench.py --full --steps 2000 --no-cpu-baseline --no-calibrate ;;
     exch)  # round 5: the exactly sized, deferred exchange (host transport + RCCL world 1) and the bench's
            # exchange path at world size 1
       step exch_tests 600 python -u -m pytest tests/test_gpu_pipeline.py tests/test_stream_split.py tests/test_gpu_parity.py \
         -m gpu -k "exchange or shard or split or dropin or coalesced" -v -p no:cacheprovider --timeout 300 \
         --timeout-method thread &&
-      step bench_exch 600 python bench.py --exchange --steps 60 --no-cpu-baseline &&
-      step bench_split 600 python bench.py --workload c3 --gib 1 --split-files --steps 5 ;;
+      step bench_exch 600 python bench.py --full --exchange --steps 60 --no-cpu-baseline &&
+      step bench_split 600 python bench.py --full --workload c3 --gib 1 --split-files --steps 5 ;;
     zsdiag)  # diagnostic zstd variants: section timers (BW_ZSTD_TIMING) and the step fences dropped
              # (build first: python backuwup_amd/build.py --ztime; build(variant="zsnofence", defines=("-DBW_ZS_NOFENCE",)))
       step zstd_ztime 600 env BW_LIB="$GRAFT_REPO_ROOT/backuwup_amd/libbackuwup_amd_ztime.so" python tools/zstd_bench.py \
