@@ -1,8 +1,10 @@
 """The CPU oracle (oracle/bw_oracle.c) pinned against everything available offline:
 published BLAKE3 known answers, the GEAR derivation rule and its sha256, the MASKS popcount
 identity, the SURVEY.md A.5 cross-check vector, and tests/golden/vectors.json produced by an
-independent pure-Python restatement (tests/golden/make_golden.py).  Parity is otherwise
-unpinned by the reference (its tests cover none of this path)."""
+independent pure-Python restatement (tests/golden/make_golden.py).  BLAKE3 is pinned to upstream
+BLAKE3 besides (tests/test_blake3_upstream.py: the C implementation inside ROCm's LLVM, through
+tests/golden/blake3_upstream.json); FastCDC's mask table is otherwise unpinned by the reference
+(its tests cover none of this path)."""
 import hashlib
 import json
 import os
