@@ -73,6 +73,17 @@ BW_BLOB_NONCE_SIZE, BW_INDEX_MAX_FILE_ENTRIES, BW_INDEX_ENTRY_BYTES = 12, 50_000
 BW_BLOB_FILE_CHUNK, BW_BLOB_TREE = 0, 1
 BW_PACK_ZSTD_STORE = 1
 
+BW_UNPACK_VERIFY = 1
+BW_UNPACK_OK, BW_UNPACK_ETAG, BW_UNPACK_EZSTD, BW_UNPACK_EDIGEST, BW_UNPACK_ERANGE = 0, 1, 2, 3, 4
+BW_BLOB_MAX_UNCOMPRESSED_SIZE = 3 * 1024 * 1024
+
+
+class BwUnpackEntry(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("packfile", ctypes.c_uint32), ("kind", ctypes.c_uint8),
+                ("compression", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2), ("length", ctypes.c_uint64),
+                ("offset", ctypes.c_uint64)]
+
+
 BW_TREE_FILE, BW_TREE_DIR = 0, 1
 BW_TREE_HAS_SIZE, BW_TREE_HAS_MTIME, BW_TREE_HAS_CTIME = 1, 2, 4
 BW_TREE_BLOB_MAX_CHILDREN = 10000
@@ -171,6 +182,16 @@ SIGNATURES = [
                                             ctypes.POINTER(BwIndexFile), ctypes.c_uint64, u64p, u64p]),
     ("bw_index_load_files", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(BwIndexFile), ctypes.c_uint64, vp,
                                            ctypes.c_uint64, u64p, u64p]),
+    ("bw_zstd_decompress_device", ctypes.c_int, [vp, vp, u64p, u64p, ctypes.c_uint64, vp, u64p, u64p, u64p, u8p]),
+    ("bw_zstd_decompress", ctypes.c_int, [vp, vp, u64p, u64p, ctypes.c_uint64, vp, u64p, u64p, u64p, u8p]),
+    ("bw_unpack_headers", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(BwPackfile), vp, ctypes.c_uint64,
+                                         ctypes.POINTER(BwUnpackEntry), ctypes.c_uint64, u64p, u64p]),
+    ("bw_unpack_blobs_device", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(BwPackfile), ctypes.c_uint64,
+                                              ctypes.POINTER(BwUnpackEntry), ctypes.c_uint64, ctypes.c_uint32, vp, u64p,
+                                              u64p, u8p]),
+    ("bw_unpack_blobs", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(BwPackfile), ctypes.c_uint64,
+                                       ctypes.POINTER(BwUnpackEntry), ctypes.c_uint64, ctypes.c_uint32, vp, u64p, u64p,
+                                       u8p]),
     ("bw_profile_enable", ctypes.c_int, [vp, ctypes.c_int]),
     ("bw_fastcdc_chunks_hashed", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint32, vp, ctypes.c_uint64, u64p, u64p]),

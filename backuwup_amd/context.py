@@ -44,6 +44,9 @@ assert TREE_BLOB_DTYPE.itemsize == ctypes.sizeof(_lib.BwTreeBlob) == 64
 PACKFILE_DTYPE = np.dtype([("first_blob", "<u8"), ("n_blobs", "<u8"), ("offset", "<u8"), ("size", "<u8"),
                            ("header_len", "<u8")])
 assert PACKFILE_DTYPE.itemsize == ctypes.sizeof(_lib.BwPackfile) == 40
+UNPACK_ENTRY_DTYPE = np.dtype([("hash", "u1", (32,)), ("packfile", "<u4"), ("kind", "u1"), ("compression", "u1"),
+                               ("pad", "u1", (2,)), ("length", "<u8"), ("offset", "<u8")])
+assert UNPACK_ENTRY_DTYPE.itemsize == ctypes.sizeof(_lib.BwUnpackEntry) == 56
 
 
 def make_tree(kind, name, size=None, mtime=None, ctime=None, children=b""):
@@ -592,6 +595,127 @@ class Context:
         check(self._L.bw_index_load_files(self.h, k, _ptr(data), tab, len(files), _ptr(out) if want_entries else None,
                                           cap if want_entries else 0, ctypes.byref(n), ctypes.byref(bad)), self.h)
         return out[:n.value] if want_entries else n.value
+
+    # -------------------------------------------------------------- the read side
+    READ_BATCH = 64  # blobs per host-form call: each takes 3 MiB of host and device room, whatever its size
+
+    def zstd_decompress(self, frames):
+        """Decompressor::decompress(frame, BLOB_MAX_UNCOMPRESSED_SIZE) with include_magicbytes(false)
+        (unpack.rs:65-67) for a list of bytes-like magicless frames, decoded on the GPU: the list
+        of their blobs, None where the reference returns Err.  A frame does not say how much it
+        regenerates, so every blob gets 3 MiB of room and the list goes through READ_BATCH at a time."""
+        res = []
+        for lo in range(0, len(frames), self.READ_BATCH):
+            res += self._zstd_decompress(frames[lo:lo + self.READ_BATCH])
+        return res
+
+    def _zstd_decompress(self, frames):
+        n = len(frames)
+        lens = np.array([len(f) for f in frames], dtype=np.uint64)
+        so = np.zeros(n, dtype=np.uint64)
+        if n > 1:
+            so[1:] = np.cumsum(lens[:-1])
+        src = np.frombuffer(b"".join(bytes(f) for f in frames) or b"\0", dtype=np.uint8)
+        cap = np.full(n, _lib.BW_BLOB_MAX_UNCOMPRESSED_SIZE, dtype=np.uint64)
+        do = np.arange(n, dtype=np.uint64) * np.uint64(_lib.BW_BLOB_MAX_UNCOMPRESSED_SIZE)
+        out = np.empty(max(n * _lib.BW_BLOB_MAX_UNCOMPRESSED_SIZE, 1), dtype=np.uint8)
+        ol, ok = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        check(self._L.bw_zstd_decompress(self.h, _ptr(src), so.ctypes.data_as(_lib.u64p), lens.ctypes.data_as(_lib.u64p),
+                                         n, _ptr(out), do.ctypes.data_as(_lib.u64p), cap.ctypes.data_as(_lib.u64p),
+                                         ol.ctypes.data_as(_lib.u64p), ok.ctypes.data_as(_lib.u8p)), self.h)
+        return [out[int(do[i]):int(do[i] + ol[i])].tobytes() if ok[i] else None for i in range(n)]
+
+    def zstd_decompress_device(self, d_src, src_off, src_len, d_dst, dst_off, dst_cap):
+        """Device pointers (ints); frame i decoded to d_dst + dst_off[i], at most dst_cap[i]
+        (<= 3 MiB) bytes.  Returns (out_len, ok) (synchronous)."""
+        so = np.ascontiguousarray(src_off, dtype=np.uint64)
+        sl = np.ascontiguousarray(src_len, dtype=np.uint64)
+        do = np.ascontiguousarray(dst_off, dtype=np.uint64)
+        dc = np.ascontiguousarray(dst_cap, dtype=np.uint64)
+        assert so.size == sl.size == do.size == dc.size
+        ol, ok = np.zeros(so.size, dtype=np.uint64), np.zeros(so.size, dtype=np.uint8)
+        check(self._L.bw_zstd_decompress_device(self.h, ctypes.c_void_p(d_src), so.ctypes.data_as(_lib.u64p),
+                                                sl.ctypes.data_as(_lib.u64p), so.size, ctypes.c_void_p(d_dst),
+                                                do.ctypes.data_as(_lib.u64p), dc.ctypes.data_as(_lib.u64p),
+                                                ol.ctypes.data_as(_lib.u64p), ok.ctypes.data_as(_lib.u8p)), self.h)
+        return ol, ok
+
+    @staticmethod
+    def _packfile_table(sizes, header_lens=None):
+        tab = (_lib.BwPackfile * max(len(sizes), 1))()
+        off = 0
+        for i, n in enumerate(sizes):
+            tab[i].offset, tab[i].size = off, n
+            if header_lens is not None:
+                tab[i].header_len = int(header_lens[i])
+            off += n
+        return tab
+
+    def unpack_headers(self, prk, packfiles, ids):
+        """The header half of Manager::get_blob (unpack.rs:27-48): packfiles = list of bytes, ids
+        their 12-byte ids.  Returns the entries of every header in packfile order (UNPACK_ENTRY_DTYPE);
+        raises BwError (BW_EFORMAT / BW_ECRYPTO) with .bad_file = the packfile's position."""
+        blobs = [bytes(b) for b in packfiles]
+        data = np.frombuffer(b"".join(blobs) or b"\0", dtype=np.uint8)
+        tab = self._packfile_table([len(b) for b in blobs])
+        idb = np.ascontiguousarray(np.frombuffer(b"".join(bytes(i) for i in ids) or b"\0" * 12, dtype=np.uint8))
+        k = (ctypes.c_uint8 * 32).from_buffer_copy(bytes(prk))
+        n, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        cap = sum(len(b) // 36 + 1 for b in blobs)
+        out = np.zeros(max(cap, 1), dtype=UNPACK_ENTRY_DTYPE)
+        rc = self._L.bw_unpack_headers(self.h, k, _ptr(data), tab, _ptr(idb), len(blobs),
+                                       out.ctypes.data_as(ctypes.POINTER(_lib.BwUnpackEntry)), cap, ctypes.byref(n),
+                                       ctypes.byref(bad))
+        if rc != _lib.BW_OK:
+            m = self._L.bw_last_error(self.h)
+            err = _lib.BwError(rc, m.decode() if m else "")
+            err.bad_file = None if bad.value == 2**64 - 1 else bad.value
+            raise err
+        return out[:n.value].copy()
+
+    def unpack_blobs(self, prk, packfiles, entries, verify=False):
+        """The blob half of Manager::get_blob (unpack.rs:52-73) for the chosen entries (from
+        unpack_headers over the same packfiles list).  Returns (blobs, status): blobs[i] the bytes or
+        None, status[i] one of _lib.BW_UNPACK_*.  verify re-hashes every blob on the GPU.  Every
+        blob gets 3 MiB of room, so the entries go through READ_BATCH at a time."""
+        blobs = [bytes(b) for b in packfiles]
+        data = np.frombuffer(b"".join(blobs) or b"\0", dtype=np.uint8)
+        hl = [int.from_bytes(b[:8], "little") if len(b) >= 8 else 0 for b in blobs]
+        tab = self._packfile_table([len(b) for b in blobs], hl)
+        en = np.ascontiguousarray(entries, dtype=UNPACK_ENTRY_DTYPE)
+        k = (ctypes.c_uint8 * 32).from_buffer_copy(bytes(prk))
+        res, status = [], np.zeros(en.size, dtype=np.uint8)
+        for lo in range(0, en.size, self.READ_BATCH):
+            part = np.ascontiguousarray(en[lo:lo + self.READ_BATCH])
+            n = part.size
+            do = np.arange(n, dtype=np.uint64) * np.uint64(_lib.BW_BLOB_MAX_UNCOMPRESSED_SIZE)
+            out = np.empty(n * _lib.BW_BLOB_MAX_UNCOMPRESSED_SIZE, dtype=np.uint8)
+            ol, st = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+            check(self._L.bw_unpack_blobs(self.h, k, _ptr(data), tab, len(blobs),
+                                          part.ctypes.data_as(ctypes.POINTER(_lib.BwUnpackEntry)), n,
+                                          _lib.BW_UNPACK_VERIFY if verify else 0, _ptr(out), do.ctypes.data_as(_lib.u64p),
+                                          ol.ctypes.data_as(_lib.u64p), st.ctypes.data_as(_lib.u8p)), self.h)
+            res += [out[int(do[i]):int(do[i] + ol[i])].tobytes() if st[i] == _lib.BW_UNPACK_OK else None for i in range(n)]
+            status[lo:lo + n] = st
+        return res, status
+
+    def unpack_blobs_device(self, prk, d_packfiles, plan, entries, d_dst, dst_off, verify=False):
+        """bw_unpack_blobs_device: packfiles in device memory (pointer d_packfiles, plan = their
+        PACKFILE_DTYPE table with offset, size and header_len), blobs decoded to d_dst + dst_off[i]
+        (3 MiB of room each).  Returns (out_len, status) (synchronous)."""
+        pl = np.ascontiguousarray(plan, dtype=PACKFILE_DTYPE)
+        en = np.ascontiguousarray(entries, dtype=UNPACK_ENTRY_DTYPE)
+        do = np.ascontiguousarray(dst_off, dtype=np.uint64)
+        assert do.size == en.size
+        k = (ctypes.c_uint8 * 32).from_buffer_copy(bytes(prk))
+        ol, st = np.zeros(en.size, dtype=np.uint64), np.zeros(en.size, dtype=np.uint8)
+        check(self._L.bw_unpack_blobs_device(self.h, k, ctypes.c_void_p(d_packfiles),
+                                             pl.ctypes.data_as(ctypes.POINTER(_lib.BwPackfile)), pl.size,
+                                             en.ctypes.data_as(ctypes.POINTER(_lib.BwUnpackEntry)), en.size,
+                                             _lib.BW_UNPACK_VERIFY if verify else 0, ctypes.c_void_p(d_dst),
+                                             do.ctypes.data_as(_lib.u64p), ol.ctypes.data_as(_lib.u64p),
+                                             st.ctypes.data_as(_lib.u8p)), self.h)
+        return ol, st
 
     # -------------------------------------------------------------- stage timing
     def profile_enable(self, on=True):

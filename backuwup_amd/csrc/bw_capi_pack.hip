@@ -19,6 +19,7 @@
 #include "bw_device.h"
 #include "bw_internal.h"
 #include "bw_ctx.h"
+#include "bw_unpack.h"
 
 using namespace bw;
 
@@ -766,4 +767,285 @@ extern "C" int bw_index_load_files(bw_ctx* c, const uint8_t prk[32], const uint8
     if (entries) HIPCHK(c, hipMemcpyAsync(entries, rec, R * BW_INDEX_ENTRY_BYTES, hipMemcpyDeviceToHost, c->stream));
     if (int rc = dedup_device(c, dig, nullptr, R, R, nullptr)) return rc;
     return check_collision(c);
+}
+
+// ------------------------------------------------------------------ the read side (§8f row 5)
+// Manager::get_blob's data path (unpack.rs:23-83); kernels in bw_zstd_dec.hip.  These calls are
+// synchronous and keep no state between calls, so they work in the buffers the context already owns
+// for the synchronous calls of the write side: the index loader's (ix_io, ix_tab, ix_dig: tables,
+// header plaintexts, the decoder's literals buffers), the host forms' staging (zs_io; pk_out for
+// packfiles, pk_src for blobs) and bw_pack_compress_device's frame staging (pk_stage).
+// Memory: a frame without Frame_Content_Size does not say how much it regenerates, so the host forms
+// reserve BLOB_MAX_UNCOMPRESSED_SIZE (3 MiB) of device memory per blob (callers of the device forms
+// choose their own layout), and the decoder keeps one 128 KiB literals buffer per wave, at most
+// ZD_MAX_WAVES of them (256 MiB from 2,048 frames up).  Large restores go through in batches.
+
+// frames (device) -> blobs (device); status (host, optional) = zd::Err per frame
+static int zd_run(bw_ctx* c, const uint8_t* d_src, const uint64_t* src_off, const uint64_t* src_len, uint64_t n,
+                  uint8_t* d_dst, const uint64_t* dst_off, const uint64_t* dst_cap, uint64_t* out_len,
+                  std::vector<uint32_t>& status) {
+    status.assign(n, 0);
+    if (!n) return BW_OK;
+    std::vector<ZdItem> items(n);
+    for (uint64_t i = 0; i < n; i++) items[i] = ZdItem{src_off[i], src_len[i], dst_off[i], dst_cap[i]};
+    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, ZD_MAX_WAVES);
+    const uint64_t tab = n * sizeof(ZdItem), res = n * 8;
+    if (int rc = ensure(c, c->ix_tab, tab + res + n * 4)) return rc;
+    if (int rc = ensure(c, c->ix_dig, waves * ZD_LIT_STRIDE)) return rc;
+    uint8_t* t = P<uint8_t>(c->ix_tab);
+    // pageable source: the copy has left `items` when hipMemcpyAsync returns
+    HIPCHK(c, hipMemcpyAsync(t, items.data(), tab, hipMemcpyHostToDevice, c->stream));
+    launch_zd_frames(c->stream, d_src, d_dst, (const ZdItem*)t, n, waves, P<uint8_t>(c->ix_dig), (uint64_t*)(t + tab),
+                     (uint32_t*)(t + tab + res));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_len, t + tab, res, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status.data(), t + tab + res, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BW_OK;
+}
+
+extern "C" int bw_zstd_decompress_device(bw_ctx* c, const uint8_t* d_src, const uint64_t* src_off,
+                                         const uint64_t* src_len, uint64_t n, uint8_t* d_dst, const uint64_t* dst_off,
+                                         const uint64_t* dst_cap, uint64_t* out_len, uint8_t* ok) {
+    if (!c || (n && (!d_src || !src_off || !src_len || !d_dst || !dst_off || !dst_cap || !out_len || !ok)))
+        return BW_EINVAL;
+    for (uint64_t i = 0; i < n; i++)
+        if (dst_cap[i] > BW_BLOB_MAX_UNCOMPRESSED_SIZE) {
+            c->err = "zstd: capacity of blob " + std::to_string(i) + " above BLOB_MAX_UNCOMPRESSED_SIZE (3 MiB)";
+            return BW_EINVAL;
+        }
+    if (!n) return BW_OK;
+    hipSetDevice(c->device);
+    std::vector<uint32_t> st;
+    if (int rc = zd_run(c, d_src, src_off, src_len, n, d_dst, dst_off, dst_cap, out_len, st)) return rc;
+    for (uint64_t i = 0; i < n; i++) ok[i] = st[i] == 0;
+    return BW_OK;
+}
+
+extern "C" int bw_zstd_decompress(bw_ctx* c, const uint8_t* src, const uint64_t* src_off, const uint64_t* src_len,
+                                  uint64_t n, uint8_t* dst, const uint64_t* dst_off, const uint64_t* dst_cap,
+                                  uint64_t* out_len, uint8_t* ok) {
+    if (!c || (n && (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out_len || !ok))) return BW_EINVAL;
+    // frames packed back to back on the device, each blob's capacity behind them
+    std::vector<uint64_t> so(n), dof(n);
+    uint64_t in = 0, out = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (dst_cap[i] > BW_BLOB_MAX_UNCOMPRESSED_SIZE) return BW_EINVAL;
+        so[i] = in;
+        in += (src_len[i] + 15) & ~15ull;
+        dof[i] = out;
+        out += (dst_cap[i] + 15) & ~15ull;
+    }
+    if (!n) return BW_OK;
+    hipSetDevice(c->device);
+    if (int rc = ensure(c, c->zs_io, in + out + 16)) return rc;
+    uint8_t* io = P<uint8_t>(c->zs_io);
+    for (uint64_t i = 0; i < n; i++)
+        if (src_len[i]) HIPCHK(c, hipMemcpyAsync(io + so[i], src + src_off[i], src_len[i], hipMemcpyHostToDevice, c->stream));
+    if (int rc = bw_zstd_decompress_device(c, io, so.data(), src_len, n, io + in, dof.data(), dst_cap, out_len, ok)) return rc;
+    for (uint64_t i = 0; i < n; i++)
+        if (ok[i] && out_len[i])
+            HIPCHK(c, hipMemcpyAsync(dst + dst_off[i], io + in + dof[i], out_len[i], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BW_OK;
+}
+
+extern "C" int bw_unpack_headers(bw_ctx* c, const uint8_t prk[32], const uint8_t* data, const bw_packfile* pf,
+                                 const uint8_t* ids, uint64_t npf, bw_unpack_entry* entries, uint64_t cap,
+                                 uint64_t* n_entries, uint64_t* bad_file) {
+    if (!c || !prk || !n_entries || (npf && (!data || !pf || !ids)) || (cap && !entries)) return BW_EINVAL;
+    *n_entries = 0;
+    if (bad_file) *bad_file = ~0ull;
+    if (!npf) return BW_OK;
+    auto fail = [&](uint64_t p, int rc, const std::string& why) {
+        if (bad_file) *bad_file = p;
+        c->err = "packfile " + std::to_string(p) + ": " + why;
+        return rc;
+    };
+    std::vector<uint64_t> src_off(npf), src_len(npf), pt_off(npf), pt_len(npf);
+    std::vector<uint8_t> info(6 * npf);
+    uint64_t ct_total = 0, pt_total = 0;
+    for (uint64_t p = 0; p < npf; p++) {
+        if (pf[p].size > BW_PACKFILE_MAX_SIZE) return fail(p, BW_EFORMAT, "PackfileTooLarge");
+        if (pf[p].size < 8) return fail(p, BW_EFORMAT, "shorter than its header size field");
+        uint64_t hl;
+        memcpy(&hl, data + pf[p].offset, 8);  // u64 LE (the library's hosts are little-endian)
+        if (hl > pf[p].size || hl == 0) return fail(p, BW_EFORMAT, "InvalidHeaderSize");
+        if (hl > pf[p].size - 8) return fail(p, BW_EFORMAT, "header runs past the packfile");  // read_exact fails
+        if (hl < BW_SEAL_TAG_BYTES) return fail(p, BW_ECRYPTO, "header shorter than the GCM tag");
+        src_off[p] = ct_total;
+        src_len[p] = hl;
+        ct_total += (hl + 15) & ~15ull;
+        pt_off[p] = pt_total;
+        pt_len[p] = hl - BW_SEAL_TAG_BYTES;
+        pt_total += (pt_len[p] + 15) & ~15ull;
+        memcpy(&info[6 * p], "header", 6);
+    }
+    hipSetDevice(c->device);
+    const uint64_t pt_base = (ct_total + 255) & ~255ull;
+    if (int rc = ensure(c, c->ix_io, pt_base + pt_total + 16)) return rc;
+    uint8_t* io = P<uint8_t>(c->ix_io);
+    for (uint64_t p = 0; p < npf; p++)
+        HIPCHK(c, hipMemcpyAsync(io + src_off[p], data + pf[p].offset + 8, src_len[p], hipMemcpyHostToDevice, c->stream));
+    std::vector<uint8_t> ok(npf);
+    if (int rc = seal_submit(c, true, prk, io, src_off.data(), src_len.data(), npf, info.data(), 6, ids, io + pt_base,
+                             pt_off.data(), ok.data()))
+        return rc;
+    for (uint64_t p = 0; p < npf; p++)
+        if (!ok[p]) return fail(p, BW_ECRYPTO, "header failed authentication");
+    // count, then gather
+    if (int rc = ensure(c, c->ix_tab, npf * 8 * 4)) return rc;
+    uint64_t* tab = P<uint64_t>(c->ix_tab);
+    std::vector<uint64_t> up(3 * npf);
+    std::copy(pt_off.begin(), pt_off.end(), up.begin());
+    std::copy(pt_len.begin(), pt_len.end(), up.begin() + npf);
+    HIPCHK(c, hipMemcpyAsync(tab, up.data(), 2 * npf * 8, hipMemcpyHostToDevice, c->stream));
+    launch_unpack_parse(c->stream, io + pt_base, tab, tab + npf, npf, nullptr, tab + 3 * npf, nullptr);
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint64_t> parsed(npf);
+    HIPCHK(c, hipMemcpyAsync(parsed.data(), tab + 3 * npf, npf * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint64_t R = 0;
+    for (uint64_t p = 0; p < npf; p++) {
+        if (parsed[p] == ~0ull) return fail(p, BW_EFORMAT, "header is not a bincode Vec<PackfileHeaderBlob>");
+        up[2 * npf + p] = R;
+        R += parsed[p];
+    }
+    *n_entries = R;
+    if (cap < R) return BW_ENOSPC;
+    if (!R) return BW_OK;
+    HIPCHK(c, hipMemcpyAsync(tab + 2 * npf, up.data() + 2 * npf, npf * 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = ensure(c, c->ix_dig, R * sizeof(bw_unpack_entry))) return rc;
+    launch_unpack_parse(c->stream, io + pt_base, tab, tab + npf, npf, tab + 2 * npf, nullptr, P<bw_unpack_entry>(c->ix_dig));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(entries, c->ix_dig.p, R * sizeof(bw_unpack_entry), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BW_OK;
+}
+
+extern "C" int bw_unpack_blobs_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_pf, const bw_packfile* pf,
+                                      uint64_t npf, const bw_unpack_entry* entries, uint64_t n, uint32_t flags,
+                                      uint8_t* d_dst, const uint64_t* dst_off, uint64_t* out_len, uint8_t* status) {
+    if (!c || !prk || (flags & ~BW_UNPACK_VERIFY)) return BW_EINVAL;
+    if (n && (!d_pf || !pf || !npf || !entries || !d_dst || !dst_off || !out_len || !status)) return BW_EINVAL;
+    for (uint64_t i = 0; i < n; i++)
+        if (entries[i].packfile >= npf) {
+            c->err = "entry " + std::to_string(i) + " names a packfile outside the table";
+            return BW_EINVAL;
+        }
+    if (!n) return BW_OK;
+    hipSetDevice(c->device);
+    // the blobs whose nonce and sealed bytes lie inside their packfile (read_exact, unpack.rs:58-59)
+    std::vector<uint64_t> idx, s_off, s_len, f_off;
+    uint64_t stage = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const bw_unpack_entry& e = entries[i];
+        const bw_packfile& f = pf[e.packfile];
+        out_len[i] = 0;
+        const uint64_t base = 8 + f.header_len;
+        if (base > f.size || e.offset > f.size - base || BW_BLOB_NONCE_SIZE > f.size - base - e.offset ||
+            e.length > f.size - base - e.offset - BW_BLOB_NONCE_SIZE || e.length < BW_SEAL_TAG_BYTES) {
+            status[i] = BW_UNPACK_ERANGE;
+            continue;
+        }
+        status[i] = BW_UNPACK_OK;
+        idx.push_back(i);
+        s_off.push_back(f.offset + base + e.offset + BW_BLOB_NONCE_SIZE);
+        s_len.push_back(e.length);
+        f_off.push_back(stage);
+        stage += (e.length - BW_SEAL_TAG_BYTES + 15) & ~15ull;
+    }
+    const uint64_t m = idx.size();
+    if (!m) return BW_OK;
+    // the nonces come out of the packfiles: 12 bytes each, behind the staged frames
+    c->pk_stage_off.clear();  // frames bw_pack_compress_device staged here are gone
+    c->pk_stage_len.clear();
+    const uint64_t nonce_base = (stage + 255) & ~255ull;
+    if (int rc = ensure(c, c->pk_stage, nonce_base + 12 * m + 16)) return rc;
+    uint8_t* stg = P<uint8_t>(c->pk_stage);
+    std::vector<uint64_t> n_off(m);
+    for (uint64_t k = 0; k < m; k++) n_off[k] = s_off[k] - BW_BLOB_NONCE_SIZE;
+    if (int rc = ensure(c, c->ix_tab, m * 8)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->ix_tab.p, n_off.data(), m * 8, hipMemcpyHostToDevice, c->stream));
+    launch_gather12(c->stream, d_pf, P<uint64_t>(c->ix_tab), m, stg + nonce_base);
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint8_t> nonces(12 * m), hashes(32 * m), ok(m);
+    HIPCHK(c, hipMemcpyAsync(nonces.data(), stg + nonce_base, 12 * m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint64_t k = 0; k < m; k++) memcpy(&hashes[32 * k], entries[idx[k]].hash, 32);
+    if (int rc = seal_submit(c, true, prk, d_pf, s_off.data(), s_len.data(), m, hashes.data(), 32, nonces.data(), stg,
+                             f_off.data(), ok.data()))
+        return rc;
+    // frames whose tag verified -> blobs
+    std::vector<uint64_t> z_idx, z_off, z_len, z_dst, z_cap;
+    for (uint64_t k = 0; k < m; k++) {
+        if (!ok[k]) {
+            status[idx[k]] = BW_UNPACK_ETAG;
+            continue;
+        }
+        z_idx.push_back(idx[k]);
+        z_off.push_back(f_off[k]);
+        z_len.push_back(s_len[k] - BW_SEAL_TAG_BYTES);
+        z_dst.push_back(dst_off[idx[k]]);
+        z_cap.push_back(BW_BLOB_MAX_UNCOMPRESSED_SIZE);
+    }
+    const uint64_t z = z_idx.size();
+    std::vector<uint64_t> z_out(z);
+    std::vector<uint32_t> st;
+    if (int rc = zd_run(c, stg, z_off.data(), z_len.data(), z, d_dst, z_dst.data(), z_cap.data(), z_out.data(), st)) return rc;
+    std::vector<uint64_t> h_idx, h_off, h_len;
+    uint64_t d_end = 0;
+    for (uint64_t k = 0; k < z; k++) {
+        if (st[k]) {
+            status[z_idx[k]] = BW_UNPACK_EZSTD;
+            continue;
+        }
+        out_len[z_idx[k]] = z_out[k];
+        h_idx.push_back(z_idx[k]);
+        h_off.push_back(z_dst[k]);
+        h_len.push_back(z_out[k]);
+        d_end = std::max(d_end, z_dst[k] + z_out[k]);
+    }
+    if (!(flags & BW_UNPACK_VERIFY) || h_idx.empty()) return BW_OK;
+    // verify after read: BLAKE3 of every regenerated blob on the device against its entry's hash
+    bw_params p;
+    bw_params_default(&p);
+    p.flags = BW_F_NO_DEDUP;
+    p.small_file_threshold = ~0ull;  // every blob is hashed whole
+    uint64_t ticket = 0, got = 0;
+    std::vector<bw_blob> rec(h_idx.size());
+    if (int rc = bw_submit_device(c, d_dst, d_end, h_off.data(), h_len.data(), h_idx.size(), &p, &ticket)) return rc;
+    if (int rc = bw_wait(c, ticket, rec.data(), rec.size(), &got)) return rc;
+    if (got != h_idx.size()) {
+        c->err = "verify: the hash pass returned another number of blobs";
+        return BW_EHIP;
+    }
+    for (uint64_t k = 0; k < got; k++)
+        if (memcmp(rec[k].digest, entries[h_idx[k]].hash, 32)) status[h_idx[k]] = BW_UNPACK_EDIGEST;
+    return BW_OK;
+}
+
+extern "C" int bw_unpack_blobs(bw_ctx* c, const uint8_t prk[32], const uint8_t* data, const bw_packfile* pf, uint64_t npf,
+                               const bw_unpack_entry* entries, uint64_t n, uint32_t flags, uint8_t* dst,
+                               const uint64_t* dst_off, uint64_t* out_len, uint8_t* status) {
+    if (!c || !prk || (flags & ~BW_UNPACK_VERIFY)) return BW_EINVAL;
+    if (n && (!data || !pf || !npf || !entries || !dst || !dst_off || !out_len || !status)) return BW_EINVAL;
+    if (!n) return BW_OK;
+    hipSetDevice(c->device);
+    uint64_t end = 0;
+    for (uint64_t p = 0; p < npf; p++) end = std::max(end, pf[p].offset + pf[p].size);
+    std::vector<uint64_t> dof(n);
+    for (uint64_t i = 0; i < n; i++) dof[i] = i * (uint64_t)BW_BLOB_MAX_UNCOMPRESSED_SIZE;
+    if (int rc = ensure(c, c->pk_out, end + 16)) return rc;
+    if (int rc = ensure(c, c->pk_src, n * (uint64_t)BW_BLOB_MAX_UNCOMPRESSED_SIZE + 16)) return rc;
+    if (end) HIPCHK(c, hipMemcpyAsync(c->pk_out.p, data, end, hipMemcpyHostToDevice, c->stream));
+    if (int rc = bw_unpack_blobs_device(c, prk, P<uint8_t>(c->pk_out), pf, npf, entries, n, flags, P<uint8_t>(c->pk_src),
+                                        dof.data(), out_len, status))
+        return rc;
+    for (uint64_t i = 0; i < n; i++)
+        if ((status[i] == BW_UNPACK_OK || status[i] == BW_UNPACK_EDIGEST) && out_len[i])
+            HIPCHK(c, hipMemcpyAsync(dst + dst_off[i], P<uint8_t>(c->pk_src) + dof[i], out_len[i], hipMemcpyDeviceToHost,
+                                     c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BW_OK;
 }

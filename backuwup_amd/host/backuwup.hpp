@@ -352,6 +352,92 @@ inline std::vector<std::pair<PackfileId, std::vector<uint8_t>>> write_packfiles_
     return res;
 }
 
+// ------------------------------------------------------------------ the read side (unpack.rs:23-83)
+// Decompressor::decompress(frame, BLOB_MAX_UNCOMPRESSED_SIZE) with include_magicbytes(false)
+// (unpack.rs:65-67) for every frame, on the GPU: ok[i] false where the reference returns Err.
+// A frame does not say how much it regenerates: 3 MiB of host and device room per frame, so pass
+// a few hundred frames at a time.
+inline std::vector<std::vector<uint8_t>> zstd_decompress(Context& ctx, const std::vector<std::vector<uint8_t>>& frames,
+                                                         std::vector<bool>* ok_out = nullptr) {
+    const uint64_t cap = BW_BLOB_MAX_UNCOMPRESSED_SIZE;
+    std::vector<uint64_t> so, sl, dof, dc(frames.size(), cap), ol(frames.size());
+    std::vector<uint8_t> src, ok(frames.size()), dst(frames.size() * cap + 1);
+    for (size_t i = 0; i < frames.size(); i++) {
+        so.push_back(src.size());
+        sl.push_back(frames[i].size());
+        dof.push_back(i * cap);
+        src.insert(src.end(), frames[i].begin(), frames[i].end());
+    }
+    static const uint8_t none[1] = {0};
+    check(bw_zstd_decompress(ctx.get(), src.empty() ? none : src.data(), so.data(), sl.data(), frames.size(), dst.data(),
+                             dof.data(), dc.data(), ol.data(), ok.data()),
+          ctx.get());
+    std::vector<std::vector<uint8_t>> out(frames.size());
+    if (ok_out) ok_out->assign(frames.size(), false);
+    for (size_t i = 0; i < frames.size(); i++) {
+        if (!ok[i]) continue;
+        out[i].assign(dst.begin() + dof[i], dst.begin() + dof[i] + ol[i]);
+        if (ok_out) (*ok_out)[i] = true;
+    }
+    return out;
+}
+
+struct PackfileTable {  // packfiles laid out back to back, as the bw_unpack_* calls take them
+    std::vector<uint8_t> data, ids;
+    std::vector<bw_packfile> tab;
+};
+
+inline PackfileTable packfile_table(const std::vector<std::pair<PackfileId, std::vector<uint8_t>>>& packfiles) {
+    PackfileTable t;
+    for (const auto& p : packfiles) {
+        bw_packfile f{};
+        f.offset = t.data.size();
+        f.size = p.second.size();
+        for (int k = 0; k < 8 && (size_t)k < p.second.size(); k++) f.header_len |= (uint64_t)p.second[k] << (8 * k);
+        t.tab.push_back(f);
+        t.data.insert(t.data.end(), p.second.begin(), p.second.end());
+        t.ids.insert(t.ids.end(), p.first.begin(), p.first.end());
+    }
+    return t;
+}
+
+// The header half of Manager::get_blob (unpack.rs:27-48): every packfile's entries, in order.
+inline std::vector<bw_unpack_entry> unpack_headers(Context& ctx, const std::array<uint8_t, 32>& prk, const PackfileTable& t) {
+    uint64_t n = 0, bad = 0;
+    const int rc = bw_unpack_headers(ctx.get(), prk.data(), t.data.data(), t.tab.data(), t.ids.data(), t.tab.size(), nullptr,
+                                     0, &n, &bad);
+    if (rc != BW_ENOSPC) check(rc, ctx.get());
+    std::vector<bw_unpack_entry> out(n);
+    if (n)
+        check(bw_unpack_headers(ctx.get(), prk.data(), t.data.data(), t.tab.data(), t.ids.data(), t.tab.size(), out.data(), n,
+                                &n, &bad),
+              ctx.get());
+    return out;
+}
+
+// The blob half (unpack.rs:52-73) for the chosen entries: blob i and status[i] (BW_UNPACK_*);
+// verify re-hashes every blob on the GPU against its entry's hash.  3 MiB of host and device room per
+// entry: pass a few hundred entries at a time.
+inline std::vector<Blob> unpack_blobs(Context& ctx, const std::array<uint8_t, 32>& prk, const PackfileTable& t,
+                                      const std::vector<bw_unpack_entry>& entries, bool verify,
+                                      std::vector<uint8_t>* status_out = nullptr) {
+    const uint64_t cap = BW_BLOB_MAX_UNCOMPRESSED_SIZE;
+    std::vector<uint64_t> dof, ol(entries.size());
+    std::vector<uint8_t> st(entries.size()), dst(entries.size() * cap + 1);
+    for (size_t i = 0; i < entries.size(); i++) dof.push_back(i * cap);
+    check(bw_unpack_blobs(ctx.get(), prk.data(), t.data.data(), t.tab.data(), t.tab.size(), entries.data(), entries.size(),
+                          verify ? BW_UNPACK_VERIFY : 0, dst.data(), dof.data(), ol.data(), st.data()),
+          ctx.get());
+    std::vector<Blob> out(entries.size());
+    for (size_t i = 0; i < entries.size(); i++) {
+        std::copy(entries[i].hash, entries[i].hash + 32, out[i].hash.begin());
+        out[i].kind = (BlobKind)entries[i].kind;
+        if (st[i] == BW_UNPACK_OK) out[i].data.assign(dst.begin() + dof[i], dst.begin() + dof[i] + ol[i]);
+    }
+    if (status_out) *status_out = st;
+    return out;
+}
+
 // ------------------------------------------------------------------ index files (blob_index.rs)
 using IndexEntry = std::pair<BlobHash, PackfileId>;
 

@@ -16,12 +16,17 @@ import numpy as np
 from .context import (BLOB_DESIRED_TARGET_SIZE, BLOB_MAX_UNCOMPRESSED_SIZE, BLOB_MINIMUM_TARGET_SIZE,
                       BLOB_DTYPE, Context, default_context, make_params, make_tree)
 
-__all__ = ["BlobIndex", "Manager", "BlobTooLarge", "process_files", "process_file", "add_trees_to_blobs", "BLOB_DTYPE",
+__all__ = ["BlobIndex", "Manager", "BlobTooLarge", "IndexHeaderMismatch", "process_files", "process_file", "add_trees_to_blobs", "BLOB_DTYPE",
            "BLOB_MINIMUM_TARGET_SIZE", "BLOB_DESIRED_TARGET_SIZE", "BLOB_MAX_UNCOMPRESSED_SIZE"]
 
 
 class BlobTooLarge(ValueError):
     """PackfileError::BlobTooLarge (filesystem/mod.rs:80-105, raised at pack.rs:32-34)."""
+
+
+class IndexHeaderMismatch(LookupError):
+    """PackfileError::IndexHeaderMismatch (unpack.rs:77): the index names a packfile whose header
+    does not list the blob."""
 
 
 class BlobIndex:
@@ -50,11 +55,58 @@ class BlobIndex:
 
 
 class Manager:
-    """The dedup gate of packfile::Manager (pack.rs:31-55); compression/encryption/packfile
-    writing downstream of the gate are out of scope and unchanged."""
+    """The dedup gate of packfile::Manager (pack.rs:31-55) and its read path (get_blob,
+    unpack.rs:23-83) over an index and a store of packfiles held in memory."""
 
-    def __init__(self, index=None, ctx=None):
+    def __init__(self, index=None, ctx=None, blob_packfiles=None, packfiles=None, prk=None):
+        """blob_packfiles: {blob hash: packfile id} (BlobIndex::find_packfile), packfiles: {packfile
+        id: bytes} and prk (the backup secret key) serve get_blob / get_blobs; the gate needs none."""
         self.index = index or BlobIndex(ctx=ctx)
+        self.blob_packfiles = dict(blob_packfiles or {})
+        self.packfiles = dict(packfiles or {})
+        self.prk = prk
+
+    def get_blob(self, blob_hash, verify=False):
+        """Manager::get_blob (unpack.rs:23-83): None when the index lacks the hash,
+        IndexHeaderMismatch when the packfile's header lacks it, else (kind, data).  Header and
+        blob are opened, and the frame decoded, on the GPU."""
+        return self.get_blobs([blob_hash], verify)[0]
+
+    def get_blobs(self, hashes, verify=False):
+        """get_blob for many hashes, grouped by packfile: every packfile's header is opened once
+        and all wanted blobs are opened and decoded in one batch.  A blob whose tag, frame or (with
+        verify) digest fails raises ValueError, as the reference returns Err."""
+        from . import _lib
+        hashes = [bytes(h) for h in hashes]
+        ids = []
+        for h in hashes:  # the packfiles to open, in first-use order
+            pid = self.blob_packfiles.get(h)
+            if pid is not None and bytes(pid) not in ids:
+                ids.append(bytes(pid))
+        out = [None] * len(hashes)
+        if not ids:
+            return out
+        ctx = self.index.ctx
+        files = [self.packfiles[i] for i in ids]
+        entries = ctx.unpack_headers(self.prk, files, ids)
+        where = {(int(e["packfile"]), e["hash"].tobytes()): k for k, e in reversed(list(enumerate(entries)))}
+        want, slots = [], []
+        for pos, h in enumerate(hashes):
+            pid = self.blob_packfiles.get(h)
+            if pid is None:
+                continue
+            k = where.get((ids.index(bytes(pid)), h))
+            if k is None:
+                raise IndexHeaderMismatch(h.hex())
+            want.append(k)
+            slots.append(pos)
+        blobs, status = ctx.unpack_blobs(self.prk, files, entries[want], verify=verify)
+        for pos, k, data, st in zip(slots, want, blobs, status):
+            if st != _lib.BW_UNPACK_OK:
+                raise ValueError("blob %s: %s" % (hashes[pos].hex(), {1: "CryptoError", 2: "zstd error", 3: "digest mismatch",
+                                                                     4: "outside its packfile"}[int(st)]))
+            out[pos] = (int(entries[k]["kind"]), data)
+        return out
 
     def add_blob(self, blob_hash, data_len):
         if data_len > BLOB_MAX_UNCOMPRESSED_SIZE:

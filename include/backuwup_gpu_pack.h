@@ -1,5 +1,6 @@
-/* backuwup_gpu_pack.h -- the C ABI of the write side after the hot path:
- * blob sealing, per-blob zstd level 3, packfiles and index files, implemented by libbackuwup_amd.so
+/* backuwup_gpu_pack.h -- the C ABI of the write side after the hot path (SURVEY.md §8f rows 2-4:
+ * blob sealing, per-blob zstd level 3, packfiles and index files) and of the read side (row 5: zstd
+ * decoding, packfile headers and blobs), implemented by libbackuwup_amd.so
  * (backuwup_amd/csrc/bw_capi_pack.hip).  Included by backuwup_gpu.h, whose types it uses; kept in a
  * file of its own so the hot path's header (and the source digest the committed profiles carry,
  * backuwup_amd/build.py) does not change when this side does. */
@@ -181,6 +182,84 @@ int bw_index_files_build(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* entr
  * BW_EFORMAT; *bad_file = its position and nothing is seeded.  Synchronous. */
 int bw_index_load_files(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* data, const bw_index_file* files,
                         uint64_t n_files, uint8_t* entries, uint64_t cap, uint64_t* n_entries, uint64_t* bad_file);
+
+/* ---- the read side ----
+ * Manager::get_blob's data path (unpack.rs:23-83): packfile header opened and parsed, blob opened,
+ * frame decoded.  The decoder is written from RFC 8878 (backuwup_amd/csrc/bw_zstd_dec_core.h): it
+ * reads every frame a zstd encoder at any level writes for one blob without a dictionary, not only
+ * what bw_zstd_compress emits.  Refused, with a per-blob error: a non-zero dictionary id, the
+ * checksum flag (the reference's Compressor never sets it, pack.rs:58-64), a reserved block type,
+ * bytes after the last block, and every malformed or truncated section.  All calls are synchronous. */
+
+/* Decompressor::new() + include_magicbytes(false) + decompress(buf, BLOB_MAX_UNCOMPRESSED_SIZE)
+ * (unpack.rs:65-67) for n magicless frames.  Frame i: d_src + src_off[i], src_len[i] bytes; its
+ * bytes go to d_dst + dst_off[i], at most dst_cap[i] (<= 3 MiB, else BW_EINVAL); out_len[i] (host)
+ * = the regenerated size; ok[i] (host) = 1, or 0 where the reference returns Err (out_len[i] = 0;
+ * the blob's output range then holds garbage).  Nothing outside [dst_off[i], dst_off[i] +
+ * dst_cap[i]) is written, whatever the frame says.  Output ranges must not overlap each other or
+ * the input.  A frame of 0 bytes decodes to 0 bytes, as ZSTD_decompressDCtx does. */
+int bw_zstd_decompress_device(bw_ctx* ctx, const uint8_t* d_src, const uint64_t* src_off, const uint64_t* src_len,
+                              uint64_t n, uint8_t* d_dst, const uint64_t* dst_off, const uint64_t* dst_cap,
+                              uint64_t* out_len, uint8_t* ok);
+/* Same over host buffers (staged through the device, which holds the frames and sum(dst_cap) bytes;
+ * only out_len[i] bytes per blob are copied back). */
+int bw_zstd_decompress(bw_ctx* ctx, const uint8_t* src, const uint64_t* src_off, const uint64_t* src_len, uint64_t n,
+                       uint8_t* dst, const uint64_t* dst_off, const uint64_t* dst_cap, uint64_t* out_len, uint8_t* ok);
+
+/* One PackfileHeaderBlob (filesystem/mod.rs:36-43) as stored, with the packfile it came from. */
+typedef struct bw_unpack_entry {
+    uint8_t hash[32];
+    uint32_t packfile;   /* position in the packfiles[] table of the call              */
+    uint8_t kind;        /* BW_BLOB_*                                                  */
+    uint8_t compression; /* CompressionKind tag as stored (0 = None, 1 = Zstd)         */
+    uint8_t pad[2];
+    uint64_t length;     /* sealed bytes (frame + 16-byte tag)                         */
+    uint64_t offset;     /* of the blob's nonce, relative to the blob section          */
+} bw_unpack_entry;
+
+/* The header half of get_blob (unpack.rs:27-48) for n_pf packfiles lying in the host buffer
+ * `data`: packfiles[p].offset / .size locate packfile p (the other fields are ignored), ids holds
+ * its 12-byte id.  Size and header_len checks on the host; headers opened (key "header", nonce =
+ * id) and parsed on the GPU, as bw_index_load_files does for index files.  entries (host, cap
+ * records) receives every header's entries in packfile order; *n_entries their number.
+ *   size > BW_PACKFILE_MAX_SIZE (PackfileTooLarge, :28), header_len == 0 or > size
+ *   (InvalidHeaderSize, :36) or past the packfile's bytes           -> BW_EFORMAT
+ *   tag mismatch (:45)                                               -> BW_ECRYPTO
+ *   not exactly one varint Vec<PackfileHeaderBlob>, enum tag above 1 -> BW_EFORMAT
+ * each with *bad_file = the packfile's position (else ~0); cap too small -> BW_ENOSPC with
+ * *n_entries set. */
+int bw_unpack_headers(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* data, const bw_packfile* packfiles,
+                      const uint8_t* ids, uint64_t n_pf, bw_unpack_entry* entries, uint64_t cap, uint64_t* n_entries,
+                      uint64_t* bad_file);
+
+/* The blob half of get_blob (unpack.rs:52-73) for n chosen entries over packfiles in device
+ * memory (d_packfiles + packfiles[p].offset, .size; .header_len must be the u64 prefix's value,
+ * as bw_pack_plan wrote it or as read from the packfile): the nonce is read at 8 + header_len +
+ * entry.offset, the blob opened with derive_backup_key(entry.hash) into a staging area the context
+ * owns (shared with bw_pack_compress_device: frames staged there are dropped), and its frame
+ * decoded to d_dst + dst_off[i] (at most BLOB_MAX_UNCOMPRESSED_SIZE = 3 MiB each; out_len[i] =
+ * the regenerated size).  entry.compression is ignored and the payload always decoded, as the
+ * reference does (unpack.rs:65-67).  With BW_UNPACK_VERIFY the regenerated bytes are hashed on the
+ * device and compared with entry.hash, which the reference never does (this runs a batch through
+ * the context's pipeline, like bw_process_files_device: wait for outstanding tickets first).
+ * status[i] (host) is one of BW_UNPACK_*; a blob failure is reported there and the call still
+ * returns BW_OK. */
+#define BW_UNPACK_VERIFY 1u
+enum {
+    BW_UNPACK_OK = 0,
+    BW_UNPACK_ETAG = 1,    /* aes_gcm::Error (unpack.rs:63)                            */
+    BW_UNPACK_EZSTD = 2,   /* the Decompressor's error (unpack.rs:67)                  */
+    BW_UNPACK_EDIGEST = 3, /* BW_UNPACK_VERIFY: BLAKE3 of the bytes != entry.hash      */
+    BW_UNPACK_ERANGE = 4   /* nonce + length outside the packfile (read_exact fails, :58-59), or length < 16 */
+};
+int bw_unpack_blobs_device(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* d_packfiles, const bw_packfile* packfiles,
+                           uint64_t n_pf, const bw_unpack_entry* entries, uint64_t n, uint32_t flags, uint8_t* d_dst,
+                           const uint64_t* dst_off, uint64_t* out_len, uint8_t* status);
+/* Same over host buffers (packfiles uploaded, blobs copied back).  A frame does not say how much it
+ * regenerates, so the call reserves 3 MiB of device memory per entry: pass a few hundred entries at a time. */
+int bw_unpack_blobs(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* packfiles_data, const bw_packfile* packfiles,
+                    uint64_t n_pf, const bw_unpack_entry* entries, uint64_t n, uint32_t flags, uint8_t* dst,
+                    const uint64_t* dst_off, uint64_t* out_len, uint8_t* status);
 
 #ifdef __cplusplus
 }

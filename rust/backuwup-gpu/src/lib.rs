@@ -151,6 +151,26 @@ pub mod ffi {
         pub n_entries: u64,
     }
 
+    /// One `PackfileHeaderBlob` as stored, with the packfile it came from (`bw_unpack_headers`).
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_unpack_entry {
+        pub hash: [u8; 32],
+        pub packfile: u32,
+        pub kind: u8,
+        pub compression: u8,
+        pub pad: [u8; 2],
+        pub length: u64,
+        pub offset: u64,
+    }
+
+    pub const BW_UNPACK_VERIFY: u32 = 1;
+    pub const BW_UNPACK_OK: u8 = 0;
+    pub const BW_UNPACK_ETAG: u8 = 1;
+    pub const BW_UNPACK_EZSTD: u8 = 2;
+    pub const BW_UNPACK_EDIGEST: u8 = 3;
+    pub const BW_UNPACK_ERANGE: u8 = 4;
+
     /// `fn(user, send, recv, bytes_per_rank)`: deliver `send[r * b ..]` to rank r's `recv[my_rank * b ..]`.
     pub type bw_host_all_to_all =
         Option<unsafe extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes_per_rank: u64) -> c_int>;
@@ -301,6 +321,24 @@ pub mod ffi {
                                    n_files: u64, entries: *mut u8, cap: u64, n_entries: *mut u64,
                                    bad_file: *mut u64) -> c_int;
 
+        pub fn bw_zstd_decompress_device(ctx: *mut bw_ctx, d_src: *const u8, src_off: *const u64, src_len: *const u64,
+                                         n: u64, d_dst: *mut u8, dst_off: *const u64, dst_cap: *const u64,
+                                         out_len: *mut u64, ok: *mut u8) -> c_int;
+        pub fn bw_zstd_decompress(ctx: *mut bw_ctx, src: *const u8, src_off: *const u64, src_len: *const u64, n: u64,
+                                  dst: *mut u8, dst_off: *const u64, dst_cap: *const u64, out_len: *mut u64,
+                                  ok: *mut u8) -> c_int;
+        pub fn bw_unpack_headers(ctx: *mut bw_ctx, prk: *const u8, data: *const u8, packfiles: *const bw_packfile,
+                                 ids: *const u8, n_pf: u64, entries: *mut bw_unpack_entry, cap: u64,
+                                 n_entries: *mut u64, bad_file: *mut u64) -> c_int;
+        pub fn bw_unpack_blobs_device(ctx: *mut bw_ctx, prk: *const u8, d_packfiles: *const u8,
+                                      packfiles: *const bw_packfile, n_pf: u64, entries: *const bw_unpack_entry, n: u64,
+                                      flags: u32, d_dst: *mut u8, dst_off: *const u64, out_len: *mut u64,
+                                      status: *mut u8) -> c_int;
+        pub fn bw_unpack_blobs(ctx: *mut bw_ctx, prk: *const u8, packfiles_data: *const u8,
+                               packfiles: *const bw_packfile, n_pf: u64, entries: *const bw_unpack_entry, n: u64,
+                               flags: u32, dst: *mut u8, dst_off: *const u64, out_len: *mut u64,
+                               status: *mut u8) -> c_int;
+
         pub fn bw_profile_enable(ctx: *mut bw_ctx, on: c_int) -> c_int;
         pub fn bw_profile_read(ctx: *mut bw_ctx, stage_ms: *mut f64, n_batches: *mut u64) -> c_int;
         pub fn bw_profile_intervals(ctx: *mut bw_ctx, stage: c_int, out: *mut f64, cap: u64, n: *mut u64) -> c_int;
@@ -419,6 +457,77 @@ impl Context {
                                      lengths.as_ptr(), offsets.len() as u64, out.as_mut_ptr() as *mut u8)
         })?;
         Ok(out)
+    }
+
+    /// `Decompressor::decompress(frame, BLOB_MAX_UNCOMPRESSED_SIZE)` with `include_magicbytes(false)`
+    /// (`unpack.rs:65-67`) for every frame, in one batch: `None` where the reference returns `Err`.
+    /// Every frame takes 3 MiB of host and device room: pass a few hundred at a time.
+    pub fn zstd_decompress(&mut self, frames: &[&[u8]]) -> Result<Vec<Option<Vec<u8>>>> {
+        const CAP: u64 = 3 * 1024 * 1024;
+        let n = frames.len();
+        let src: Vec<u8> = frames.concat();
+        let (mut so, mut at) = (Vec::with_capacity(n), 0u64);
+        for f in frames {
+            so.push(at);
+            at += f.len() as u64;
+        }
+        let sl: Vec<u64> = frames.iter().map(|f| f.len() as u64).collect();
+        let dof: Vec<u64> = (0..n as u64).map(|i| i * CAP).collect();
+        let cap = vec![CAP; n];
+        let mut dst = vec![0u8; n * CAP as usize];
+        let (mut out_len, mut ok) = (vec![0u64; n], vec![0u8; n]);
+        self.check(unsafe {
+            ffi::bw_zstd_decompress(self.raw, src.as_ptr(), so.as_ptr(), sl.as_ptr(), n as u64, dst.as_mut_ptr(),
+                                    dof.as_ptr(), cap.as_ptr(), out_len.as_mut_ptr(), ok.as_mut_ptr())
+        })?;
+        Ok((0..n).map(|i| (ok[i] != 0).then(|| dst[dof[i] as usize..(dof[i] + out_len[i]) as usize].to_vec())).collect())
+    }
+
+    /// The header half of `Manager::get_blob` (`unpack.rs:27-48`) for packfiles lying back to back
+    /// in `data` (`packfiles[p].offset / .size`), `ids[p]` their 12-byte ids.
+    pub fn unpack_headers(&mut self, prk: &[u8; 32], data: &[u8], packfiles: &[ffi::bw_packfile], ids: &[[u8; 12]])
+                          -> Result<Vec<ffi::bw_unpack_entry>> {
+        assert_eq!(packfiles.len(), ids.len());
+        let (mut n, mut bad) = (0u64, 0u64);
+        let rc = unsafe {
+            ffi::bw_unpack_headers(self.raw, prk.as_ptr(), data.as_ptr(), packfiles.as_ptr(), ids.as_ptr() as *const u8,
+                                   packfiles.len() as u64, std::ptr::null_mut(), 0, &mut n, &mut bad)
+        };
+        if rc != ffi::BW_ENOSPC {
+            self.check(rc)?;
+        }
+        let mut out = vec![ffi::bw_unpack_entry::default(); n as usize];
+        self.check(unsafe {
+            ffi::bw_unpack_headers(self.raw, prk.as_ptr(), data.as_ptr(), packfiles.as_ptr(), ids.as_ptr() as *const u8,
+                                   packfiles.len() as u64, out.as_mut_ptr(), n, &mut n, &mut bad)
+        })?;
+        Ok(out)
+    }
+
+    /// The blob half of `Manager::get_blob` (`unpack.rs:52-73`) for the chosen entries: per entry
+    /// `Ok(bytes)` or the `BW_UNPACK_*` status of its failure.  `verify` re-hashes every blob on the
+    /// GPU against its entry's hash.  Every entry takes 3 MiB of host and device room: pass a few
+    /// hundred at a time.
+    pub fn unpack_blobs(&mut self, prk: &[u8; 32], data: &[u8], packfiles: &[ffi::bw_packfile],
+                        entries: &[ffi::bw_unpack_entry], verify: bool)
+                        -> Result<Vec<std::result::Result<Vec<u8>, u8>>> {
+        const CAP: u64 = 3 * 1024 * 1024;
+        let n = entries.len();
+        let dof: Vec<u64> = (0..n as u64).map(|i| i * CAP).collect();
+        let mut dst = vec![0u8; n * CAP as usize];
+        let (mut out_len, mut status) = (vec![0u64; n], vec![0u8; n]);
+        self.check(unsafe {
+            ffi::bw_unpack_blobs(self.raw, prk.as_ptr(), data.as_ptr(), packfiles.as_ptr(), packfiles.len() as u64,
+                                 entries.as_ptr(), n as u64, if verify { ffi::BW_UNPACK_VERIFY } else { 0 },
+                                 dst.as_mut_ptr(), dof.as_ptr(), out_len.as_mut_ptr(), status.as_mut_ptr())
+        })?;
+        Ok((0..n)
+            .map(|i| if status[i] == ffi::BW_UNPACK_OK {
+                Ok(dst[dof[i] as usize..(dof[i] + out_len[i]) as usize].to_vec())
+            } else {
+                Err(status[i])
+            })
+            .collect())
     }
 
     /// `BlobIndex::load` (`blob_index.rs:167-200`): empty the index and seed it with the sorted items.
