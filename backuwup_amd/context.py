@@ -226,13 +226,18 @@ class Context:
         assert len(sl) == n and len(do) == n
         return so, sl, info, non, do, n
 
-    def seal(self, prk, src, src_off, src_len, infos, nonces, dst_off, dst_size, open_=False):
+    def seal(self, prk, src, src_off, src_len, infos, nonces, dst_off, dst_size, open_=False, out=None):
         """Host buffers: derive_backup_key(info_i) + Aes256Gcm encrypt (open_=False) or decrypt
         (open_=True).  infos: n x info_len bytes (blob hashes), nonces: n x 12.  Returns the output
-        buffer (and the ok flags when opening)."""
+        buffer (and the ok flags when opening).  out: a caller's contiguous uint8 array of at least
+        dst_size bytes to write into (only the items' output ranges are written); default a new
+        zeroed buffer."""
         buf = _as_u8(src)
         so, sl, info, non, do, n = self._seal_tables(src_off, src_len, infos, nonces, dst_off)
-        out = np.zeros(max(int(dst_size), 1), dtype=np.uint8)
+        if out is None:
+            out = np.zeros(max(int(dst_size), 1), dtype=np.uint8)
+        assert isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.ndim == 1 and \
+            out.flags.c_contiguous and out.flags.writeable and out.size >= max(int(dst_size), 1)
         k = (ctypes.c_uint8 * 32).from_buffer_copy(bytes(prk))
         args = [self.h, k, _ptr(buf), so.ctypes.data_as(_lib.u64p), sl.ctypes.data_as(_lib.u64p), n, _ptr(info),
                 info.shape[1] if n else 0, _ptr(non), _ptr(out), do.ctypes.data_as(_lib.u64p)]

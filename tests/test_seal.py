@@ -7,6 +7,13 @@ independent implementations available offline: OpenSSL libcrypto (tests/openssl_
 Python's hashlib/hmac.  GPU tests compare the HIP path (through the C ABI) with the oracle and
 OpenSSL bit for bit: ciphertext and tag, across the piece / block / partial-block edges of the
 kernels, many items per call, and tag verification on open.
+
+tests/test_gpu_seal_geometry.py adds what these batches do not reach, against OpenSSL alone:
+more than 16,384 pieces in one call (later grid-stride passes of k_seal_ctr with multi-block
+pieces, an item straddling the pass boundary), empty items anywhere in the table, info_len 0..54
+under several PRKs, every (src_off & 15, dst_off & 15) pair with canaries between the output
+ranges in the device and the host forms, a tamper matrix on open (exact ok vectors), and two
+asynchronous bw_seal_device calls in a row.
 """
 import hashlib
 import hmac
