@@ -84,6 +84,26 @@ class BwUnpackEntry(ctypes.Structure):
                 ("offset", ctypes.c_uint64)]
 
 
+BW_RESTORE_OK, BW_RESTORE_ENOTFOUND, BW_RESTORE_EMISMATCH, BW_RESTORE_ENOPACKFILE = 0, 16, 17, 18
+BW_RESTORE_ENOTTREE, BW_RESTORE_EFORMAT = 19, 20
+BW_RESTORE_SKEW_SLOTS = 0x100  # test hook: the gather's unaligned-source path
+
+
+class BwRestoreNode(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("size", ctypes.c_uint64),
+                ("mtime", ctypes.c_uint64), ("ctime", ctypes.c_uint64), ("parent", ctypes.c_uint64),
+                ("child_first", ctypes.c_uint64), ("n_children", ctypes.c_uint64), ("name_off", ctypes.c_uint64),
+                ("name_len", ctypes.c_uint64)]
+
+
+class BwRestoreCounts(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("name_bytes", ctypes.c_uint64), ("n_chunks", ctypes.c_uint64)]
+
+
+class BwRestoreError(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("reason", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
 BW_TREE_FILE, BW_TREE_DIR = 0, 1
 BW_TREE_HAS_SIZE, BW_TREE_HAS_MTIME, BW_TREE_HAS_CTIME = 1, 2, 4
 BW_TREE_BLOB_MAX_CHILDREN = 10000
@@ -192,6 +212,21 @@ SIGNATURES = [
     ("bw_unpack_blobs", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(BwPackfile), ctypes.c_uint64,
                                        ctypes.POINTER(BwUnpackEntry), ctypes.c_uint64, ctypes.c_uint32, vp, u64p, u64p,
                                        u8p]),
+    ("bw_restore_open", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(BwPackfile), vp, ctypes.c_uint64,
+                                       ctypes.POINTER(BwUnpackEntry), ctypes.c_uint64, vp, ctypes.c_uint64,
+                                       ctypes.c_uint32, ctypes.POINTER(vp)]),
+    ("bw_restore_open_host", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(BwPackfile), vp, ctypes.c_uint64,
+                                            ctypes.POINTER(BwUnpackEntry), ctypes.c_uint64, vp, ctypes.c_uint64,
+                                            ctypes.c_uint32, ctypes.POINTER(vp)]),
+    ("bw_restore_close", ctypes.c_int, [vp]),
+    ("bw_restore_locate", ctypes.c_int, [vp, vp, ctypes.c_uint64, u64p, u8p]),
+    ("bw_restore_trees", ctypes.c_int, [vp, vp, ctypes.c_uint32, ctypes.POINTER(BwRestoreNode), ctypes.c_uint64, vp,
+                                        ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(BwRestoreCounts),
+                                        ctypes.POINTER(BwRestoreError)]),
+    ("bw_restore_files_device", ctypes.c_int, [vp, vp, u64p, ctypes.c_uint64, ctypes.c_uint32, vp, ctypes.c_uint64,
+                                               u64p, u64p, u8p, u64p, u64p]),
+    ("bw_restore_files", ctypes.c_int, [vp, vp, u64p, ctypes.c_uint64, ctypes.c_uint32, vp, ctypes.c_uint64,
+                                        u64p, u64p, u8p, u64p, u64p]),
     ("bw_profile_enable", ctypes.c_int, [vp, ctypes.c_int]),
     ("bw_fastcdc_chunks_hashed", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint32, vp, ctypes.c_uint64, u64p, u64p]),

@@ -722,6 +722,18 @@ class Context:
                                              st.ctypes.data_as(_lib.u8p)), self.h)
         return ol, st
 
+    # -------------------------------------------------------------- restore (dir_unpacker.rs)
+    def restore_session(self, prk, packfiles, ids, entries, index_items, slots=0, plan=None):
+        """bw_restore_open: a restore.Session (locate, trees, files) over the packfiles (a list of
+        bytes, or a device pointer with plan = their PACKFILE_DTYPE table)."""
+        from .restore import Session
+        return Session(self, prk, packfiles, ids, entries, index_items, slots=slots, plan=plan)
+
+    def restore_unpack(self, prk, packfiles, ids, entries, index_items, root_hash, destination_dir=None, **kw):
+        """dir_unpacker::unpack (restore.unpack) on this context."""
+        from . import restore
+        return restore.unpack(self, packfiles, ids, entries, index_items, prk, root_hash, destination_dir, **kw)
+
     # -------------------------------------------------------------- stage timing
     def profile_enable(self, on=True):
         check(self._L.bw_profile_enable(self.h, 1 if on else 0), self.h)

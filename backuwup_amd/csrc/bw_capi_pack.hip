@@ -20,6 +20,7 @@
 #include "bw_internal.h"
 #include "bw_ctx.h"
 #include "bw_unpack.h"
+#include "bw_restore.h"
 
 using namespace bw;
 
@@ -780,10 +781,11 @@ extern "C" int bw_index_load_files(bw_ctx* c, const uint8_t prk[32], const uint8
 // choose their own layout), and the decoder keeps one 128 KiB literals buffer per wave, at most
 // ZD_MAX_WAVES of them (256 MiB from 2,048 frames up).  Large restores go through in batches.
 
-// frames (device) -> blobs (device); status (host, optional) = zd::Err per frame
+// frames (device) -> blobs (device); status (host, optional) = zd::Err per frame; d_res (optional)
+// receives where the n sizes (u64) lie on the device, the n statuses (u32) behind them
 static int zd_run(bw_ctx* c, const uint8_t* d_src, const uint64_t* src_off, const uint64_t* src_len, uint64_t n,
                   uint8_t* d_dst, const uint64_t* dst_off, const uint64_t* dst_cap, uint64_t* out_len,
-                  std::vector<uint32_t>& status) {
+                  std::vector<uint32_t>& status, const uint8_t** d_res = nullptr) {
     status.assign(n, 0);
     if (!n) return BW_OK;
     std::vector<ZdItem> items(n);
@@ -793,6 +795,7 @@ static int zd_run(bw_ctx* c, const uint8_t* d_src, const uint64_t* src_off, cons
     if (int rc = ensure(c, c->ix_tab, tab + res + n * 4)) return rc;
     if (int rc = ensure(c, c->ix_dig, waves * ZD_LIT_STRIDE)) return rc;
     uint8_t* t = P<uint8_t>(c->ix_tab);
+    if (d_res) *d_res = t + tab;
     // pageable source: the copy has left `items` when hipMemcpyAsync returns
     HIPCHK(c, hipMemcpyAsync(t, items.data(), tab, hipMemcpyHostToDevice, c->stream));
     launch_zd_frames(c->stream, d_src, d_dst, (const ZdItem*)t, n, waves, P<uint8_t>(c->ix_dig), (uint64_t*)(t + tab),
@@ -926,6 +929,13 @@ extern "C" int bw_unpack_headers(bw_ctx* c, const uint8_t prk[32], const uint8_t
 extern "C" int bw_unpack_blobs_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_pf, const bw_packfile* pf,
                                       uint64_t npf, const bw_unpack_entry* entries, uint64_t n, uint32_t flags,
                                       uint8_t* d_dst, const uint64_t* dst_off, uint64_t* out_len, uint8_t* status) {
+    return unpack_blobs_core(c, prk, d_pf, pf, npf, entries, n, flags, d_dst, dst_off, out_len, status, nullptr, nullptr);
+}
+
+// the restore session (bw_restore.hip) also wants the sizes where the gather reads them: d_len
+int bw::unpack_blobs_core(bw_ctx* c, const uint8_t* prk, const uint8_t* d_pf, const bw_packfile* pf, uint64_t npf,
+                          const bw_unpack_entry* entries, uint64_t n, uint32_t flags, uint8_t* d_dst,
+                          const uint64_t* dst_off, uint64_t* out_len, uint8_t* status, uint64_t* d_len, uint64_t* d_map) {
     if (!c || !prk || (flags & ~BW_UNPACK_VERIFY)) return BW_EINVAL;
     if (n && (!d_pf || !pf || !npf || !entries || !d_dst || !dst_off || !out_len || !status)) return BW_EINVAL;
     for (uint64_t i = 0; i < n; i++)
@@ -935,6 +945,7 @@ extern "C" int bw_unpack_blobs_device(bw_ctx* c, const uint8_t prk[32], const ui
         }
     if (!n) return BW_OK;
     hipSetDevice(c->device);
+    if (d_len) HIPCHK(c, hipMemsetAsync(d_len, 0, n * 8, c->stream));
     // the blobs whose nonce and sealed bytes lie inside their packfile (read_exact, unpack.rs:58-59)
     std::vector<uint64_t> idx, s_off, s_len, f_off;
     uint64_t stage = 0;
@@ -992,7 +1003,16 @@ extern "C" int bw_unpack_blobs_device(bw_ctx* c, const uint8_t prk[32], const ui
     const uint64_t z = z_idx.size();
     std::vector<uint64_t> z_out(z);
     std::vector<uint32_t> st;
-    if (int rc = zd_run(c, stg, z_off.data(), z_len.data(), z, d_dst, z_dst.data(), z_cap.data(), z_out.data(), st)) return rc;
+    const uint8_t* d_res = nullptr;
+    if (d_len && z) {  // queued before zd_run's synchronize; pageable source, copied when the call returns
+        HIPCHK(c, hipMemcpyAsync(d_map, z_idx.data(), z * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if (int rc = zd_run(c, stg, z_off.data(), z_len.data(), z, d_dst, z_dst.data(), z_cap.data(), z_out.data(), st, &d_res))
+        return rc;
+    if (d_len && z) {
+        launch_rs_scatter_lens(c->stream, (const uint64_t*)d_res, (const uint32_t*)(d_res + z * 8), d_map, z, d_len);
+        HIPCHK(c, hipGetLastError());
+    }
     std::vector<uint64_t> h_idx, h_off, h_len;
     uint64_t d_end = 0;
     for (uint64_t k = 0; k < z; k++) {

@@ -438,6 +438,122 @@ inline std::vector<Blob> unpack_blobs(Context& ctx, const std::array<uint8_t, 32
     return out;
 }
 
+// ------------------------------------------------------------------ restore (dir_unpacker.rs:14-130)
+// A session over packfiles (uploaded once) and the index items bw_index_load_files returned:
+// trees() is unpack()'s walk, files() restore_file for many files, unpack() both.
+struct RestoredFile {
+    std::string path;  // relative, components joined with '/'
+    std::vector<uint8_t> data;
+    bool has_mtime = false;
+    uint64_t mtime = 0;
+    uint8_t status = BW_RESTORE_OK;  // the first failing child's status; data is then the partial file
+    uint64_t bad_child = ~0ull;
+};
+
+struct TreeError : Error {
+    bw_restore_error what;
+    TreeError(int rc, const std::string& m, const bw_restore_error& e) : Error(rc, m), what(e) {}
+};
+
+class Restore {
+public:
+    struct Walk {
+        std::vector<bw_restore_node> nodes;
+        std::vector<uint8_t> names, chunks;
+        std::string name(size_t i) const {
+            return std::string(names.begin() + nodes[i].name_off, names.begin() + nodes[i].name_off + nodes[i].name_len);
+        }
+    };
+
+    Restore(Context& ctx, const std::array<uint8_t, 32>& prk, const PackfileTable& t,
+            const std::vector<bw_unpack_entry>& entries, const std::vector<uint8_t>& index_items, uint32_t slots = 0)
+        : ctx_(ctx) {
+        check(bw_restore_open_host(ctx.get(), prk.data(), t.data.data(), t.tab.data(), t.ids.data(), t.tab.size(),
+                                   entries.data(), entries.size(), index_items.data(),
+                                   index_items.size() / BW_INDEX_ENTRY_BYTES, slots, &s_),
+              ctx.get());
+    }
+    ~Restore() { bw_restore_close(s_); }
+    Restore(const Restore&) = delete;
+    Restore& operator=(const Restore&) = delete;
+    bw_restore* get() const { return s_; }
+
+    // entry index and status (BW_RESTORE_*) per hash
+    std::vector<uint8_t> locate(const std::vector<BlobHash>& hashes, std::vector<uint64_t>* entry_idx = nullptr) {
+        std::vector<uint8_t> h, st(hashes.size());
+        std::vector<uint64_t> idx(hashes.size());
+        for (const auto& x : hashes) h.insert(h.end(), x.begin(), x.end());
+        check(bw_restore_locate(s_, h.data(), hashes.size(), idx.data(), st.data()), ctx_.get());
+        if (entry_idx) *entry_idx = idx;
+        return st;
+    }
+
+    Walk trees(const BlobHash& root, bool verify = false) {
+        Walk w;
+        bw_restore_counts n{};
+        bw_restore_error e{};
+        const uint32_t flags = verify ? BW_UNPACK_VERIFY : 0;
+        int rc = bw_restore_trees(s_, root.data(), flags, nullptr, 0, nullptr, 0, nullptr, 0, &n, &e);
+        if (rc == BW_EFORMAT) throw TreeError(rc, "tree blob refused", e);
+        if (rc != BW_ENOSPC) check(rc, ctx_.get());
+        w.nodes.resize(n.n_nodes);
+        w.names.resize(n.name_bytes + 1);
+        w.chunks.resize(32 * (n.n_chunks + 1));
+        rc = bw_restore_trees(s_, root.data(), flags, w.nodes.data(), n.n_nodes, w.names.data(), n.name_bytes + 1,
+                              w.chunks.data(), n.n_chunks + 1, &n, &e);
+        if (rc == BW_EFORMAT) throw TreeError(rc, "tree blob refused", e);
+        check(rc, ctx_.get());
+        return w;
+    }
+
+    // dir_unpacker::unpack without the file system: every File node below the root's directories,
+    // in node order, through a window of `window` bytes (grown when one file needs more)
+    std::vector<RestoredFile> unpack(const BlobHash& root, uint64_t window = 64ull << 20, bool verify = false) {
+        const Walk w = trees(root, verify);
+        std::vector<RestoredFile> out;
+        if (w.nodes.empty() || w.nodes[0].kind != BW_TREE_DIR) return out;
+        std::vector<std::string> path(w.nodes.size());
+        std::vector<uint64_t> first{0};
+        std::vector<uint8_t> rows;
+        for (size_t i = 1; i < w.nodes.size(); i++) {
+            const bw_restore_node& nd = w.nodes[i];
+            path[i] = (nd.parent ? path[nd.parent] + "/" : std::string()) + w.name(i);
+            if (nd.kind != BW_TREE_FILE) continue;
+            RestoredFile f;
+            f.path = path[i];
+            f.has_mtime = nd.flags & BW_TREE_HAS_MTIME;
+            f.mtime = nd.mtime;
+            out.push_back(f);
+            rows.insert(rows.end(), w.chunks.begin() + 32 * nd.child_first, w.chunks.begin() + 32 * (nd.child_first + nd.n_children));
+            first.push_back(rows.size() / 32);
+        }
+        std::vector<uint8_t> buf(window);
+        size_t done = 0;
+        while (done < out.size()) {
+            const uint64_t n = out.size() - done;
+            std::vector<uint64_t> off(n), len(n), bad(n);
+            std::vector<uint8_t> st(n);
+            uint64_t got = 0;
+            const int rc = bw_restore_files(s_, rows.data(), first.data() + done, n, verify ? BW_UNPACK_VERIFY : 0, buf.data(),
+                                            buf.size(), off.data(), len.data(), st.data(), bad.data(), &got);
+            if (rc != BW_ENOSPC) check(rc, ctx_.get());
+            for (uint64_t k = 0; k < got; k++) {
+                RestoredFile& f = out[done + k];
+                f.data.assign(buf.begin() + off[k], buf.begin() + off[k] + len[k]);
+                f.status = st[k];
+                f.bad_child = bad[k];
+            }
+            done += got;
+            if (rc == BW_ENOSPC && !got) buf.resize(std::max<uint64_t>(2 * buf.size(), len[0]));
+        }
+        return out;
+    }
+
+private:
+    Context& ctx_;
+    bw_restore* s_ = nullptr;
+};
+
 // ------------------------------------------------------------------ index files (blob_index.rs)
 using IndexEntry = std::pair<BlobHash, PackfileId>;
 

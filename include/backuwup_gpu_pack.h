@@ -261,6 +261,113 @@ int bw_unpack_blobs(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* packfiles
                     uint64_t n_pf, const bw_unpack_entry* entries, uint64_t n, uint32_t flags, uint8_t* dst,
                     const uint64_t* dst_off, uint64_t* out_len, uint8_t* status);
 
+/* ---- restore: the data path of dir_unpacker.rs:14-130 ----
+ * A session over a set of packfiles in device memory does what unpack() does with data: find a
+ * blob by hash (BlobIndex::find_packfile, blob_index.rs:143-148, then the header scan of
+ * unpack.rs:50-51), walk the trees (fetch_tree, fetch_full_tree, the breadth-first queue of unpack)
+ * and assemble files from their chunks (restore_file).  Creating directories, writing files and
+ * setting mtimes stays with the caller (backuwup_amd/restore.py does it).  All calls are synchronous
+ * and use the context the session was opened on; the session owns every buffer it needs. */
+typedef struct bw_restore bw_restore;
+
+/* Per-hash and per-file statuses of a session, beside BW_UNPACK_* (which they never collide with). */
+enum {
+    BW_RESTORE_OK = 0,
+    BW_RESTORE_ENOTFOUND = 16,   /* the index lacks the hash: get_blob returns Ok(None), unpack.rs:24-26 */
+    BW_RESTORE_EMISMATCH = 17,   /* the packfile's header lacks it: IndexHeaderMismatch, unpack.rs:77    */
+    BW_RESTORE_ENOPACKFILE = 18, /* the index names a packfile id that is not among ids: File::open fails */
+    BW_RESTORE_ENOTTREE = 19,    /* a tree hash names a FileChunk blob, dir_unpacker.rs:124              */
+    BW_RESTORE_EFORMAT = 20      /* bincode::deserialize::<Tree> fails, or a chain or directory cycle    */
+};
+/* Test hook for bw_restore_files(_device): the k-th distinct blob of a call is decoded k mod 16 bytes
+ * past a 16-byte boundary, so that the gather's unaligned-source path runs (sources are 16-byte
+ * aligned otherwise). */
+#define BW_RESTORE_SKEW_SLOTS 0x100u
+
+/* packfiles / entries: as bw_unpack_headers took and returned them (d_packfiles + packfiles[p].offset,
+ * .size, .header_len; ids 12 B each); index_items: n_items x BW_INDEX_ENTRY_BYTES (BlobHash,
+ * PackfileId) records as bw_index_load_files returns them (BlobIndex.items).  slots = how many
+ * 3 MiB decode slots the session owns (0 = 1,024).  Two device tables are built, one kernel launch
+ * each: hash -> packfile position (a hash the index holds more than once resolves to any of its
+ * items, as the reference's binary search may), and (packfile position, hash) -> the lowest entry
+ * index (the header scan's first match).  Both compare whole 32-byte keys.  d_packfiles must stay
+ * valid and unchanged until bw_restore_close; the host tables are copied. */
+int bw_restore_open(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* d_packfiles, const bw_packfile* packfiles,
+                    const uint8_t* ids, uint64_t n_pf, const bw_unpack_entry* entries, uint64_t n_entries,
+                    const uint8_t* index_items, uint64_t n_items, uint32_t slots, bw_restore** out);
+/* Same over packfiles in a host buffer: the session uploads them and keeps the copy. */
+int bw_restore_open_host(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* packfiles_data, const bw_packfile* packfiles,
+                         const uint8_t* ids, uint64_t n_pf, const bw_unpack_entry* entries, uint64_t n_entries,
+                         const uint8_t* index_items, uint64_t n_items, uint32_t slots, bw_restore** out);
+int bw_restore_close(bw_restore* session);
+/* The lookup alone: entry_idx[i] = the entry of hashes[32 i ..] and status[i] = BW_RESTORE_OK, or
+ * entry_idx[i] = ~0 and status[i] = BW_RESTORE_ENOTFOUND / _EMISMATCH / _ENOPACKFILE. */
+int bw_restore_locate(bw_restore* session, const uint8_t* hashes, uint64_t n, uint64_t* entry_idx, uint8_t* status);
+
+/* One node of the walk.  Node 0 is the root; the children of a Dir node are the nodes
+ * [child_first, child_first + n_children) in child order, parents taken in node order (the order in
+ * which unpack() visits them); the children of a File node are the rows [child_first, child_first +
+ * n_children) of `chunks` (32 B each). */
+typedef struct bw_restore_node {
+    uint32_t kind;  /* BW_TREE_FILE or BW_TREE_DIR      */
+    uint32_t flags; /* BW_TREE_HAS_*                    */
+    uint64_t size, mtime, ctime;
+    uint64_t parent; /* ~0 for the root                 */
+    uint64_t child_first, n_children;
+    uint64_t name_off, name_len; /* into `names`        */
+} bw_restore_node;
+typedef struct bw_restore_counts {
+    uint64_t n_nodes, name_bytes, n_chunks;
+} bw_restore_counts;
+typedef struct bw_restore_error {
+    uint8_t hash[32]; /* the offending tree blob        */
+    uint32_t reason;  /* BW_RESTORE_* or BW_UNPACK_*    */
+    uint32_t pad;
+} bw_restore_error;
+
+/* unpack()'s walk, level by level: every level's tree blobs are located, opened and decoded through
+ * the unpack chain, parsed on the device (bincode 1.3.3 legacy deserialize: fixint little endian,
+ * u32 enum tag, u64 lengths, one-byte Option tags, trailing bytes allowed), their next_sibling
+ * chains followed one round at a time and each chain's children concatenated in chain order.
+ * flags: BW_UNPACK_VERIFY or 0.  *counts always receives what the walk needs; the arrays are filled
+ * when all three caps suffice, else BW_ENOSPC.  A tree error is fatal to the walk, as
+ * fetch_full_tree(..).await? is: BW_EFORMAT is returned and *err names the blob and the reason (a
+ * locate status, BW_UNPACK_ETAG / _EZSTD / _ERANGE / _EDIGEST, BW_RESTORE_ENOTTREE, or
+ * BW_RESTORE_EFORMAT: an enum or Option tag above 1, a name that String::from_utf8 refuses, a
+ * length that runs past the blob).
+ * Differences from the reference: it creates directories as it goes, so on an error deep in the
+ * tree it has already written the levels above; this call reports before anything is written.  It
+ * loops forever on a next_sibling cycle or a directory that contains itself; here a chain of more
+ * pieces than the store has entries, and a tree whose hash is one of its own ancestors', are
+ * BW_RESTORE_EFORMAT.  A root of kind File yields one node and its chunk rows; the reference
+ * restores nothing from it. */
+int bw_restore_trees(bw_restore* session, const uint8_t root_hash[32], uint32_t flags, bw_restore_node* nodes,
+                     uint64_t node_cap, uint8_t* names, uint64_t names_cap, uint8_t* chunks, uint64_t chunks_cap,
+                     bw_restore_counts* counts, bw_restore_error* err);
+
+/* restore_file (dir_unpacker.rs:75-92) for n_files files: file f is the concatenation of the blobs
+ * named by rows file_first[f] .. file_first[f + 1] of chunks (host, 32 B each); the files land back
+ * to back in d_dst, file_off[f] / file_len[f] (host) say where.  The children go through in file
+ * order in sub-batches of at most `slots` distinct blobs, each located, opened and decoded once per
+ * sub-batch however often it is named; the instances' places come from a scan of the regenerated
+ * sizes on the device, and one gather kernel copies them.  flags: BW_UNPACK_VERIFY,
+ * BW_RESTORE_SKEW_SLOTS.
+ * Failures are per file, as the reference prints them and carries on (dir_unpacker.rs:58-63):
+ * file_status[f] = the first failing child's status (a locate status or BW_UNPACK_*),
+ * file_bad_child[f] = its position in the file (~0 when none), file_len[f] = the bytes of the
+ * children before it, which is the partial file the reference leaves behind.
+ * dst_cap is a window: when a file does not fit behind the ones before it, the call returns
+ * BW_ENOSPC with *n_done = the whole files written (the caller drains them and calls again with
+ * the rest) and file_len[*n_done] = that file's size as far as the sub-batch showed it.  Nothing
+ * outside [d_dst, d_dst + dst_cap) is written.  Otherwise *n_done = n_files. */
+int bw_restore_files_device(bw_restore* session, const uint8_t* chunks, const uint64_t* file_first, uint64_t n_files,
+                            uint32_t flags, uint8_t* d_dst, uint64_t dst_cap, uint64_t* file_off, uint64_t* file_len,
+                            uint8_t* file_status, uint64_t* file_bad_child, uint64_t* n_done);
+/* Same into a host buffer (the files are copied back from a window the session owns). */
+int bw_restore_files(bw_restore* session, const uint8_t* chunks, const uint64_t* file_first, uint64_t n_files,
+                     uint32_t flags, uint8_t* dst, uint64_t dst_cap, uint64_t* file_off, uint64_t* file_len,
+                     uint8_t* file_status, uint64_t* file_bad_child, uint64_t* n_done);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,52 @@ pub mod ffi {
     pub const BW_UNPACK_EDIGEST: u8 = 3;
     pub const BW_UNPACK_ERANGE: u8 = 4;
 
+    /// A restore session over a set of packfiles (`bw_restore_open`).
+    #[repr(C)]
+    pub struct bw_restore {
+        _private: [u8; 0],
+    }
+
+    /// One node of `bw_restore_trees`' walk, in the order `dir_unpacker::unpack` visits them.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_restore_node {
+        pub kind: u32,
+        pub flags: u32,
+        pub size: u64,
+        pub mtime: u64,
+        pub ctime: u64,
+        pub parent: u64,
+        pub child_first: u64,
+        pub n_children: u64,
+        pub name_off: u64,
+        pub name_len: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_restore_counts {
+        pub n_nodes: u64,
+        pub name_bytes: u64,
+        pub n_chunks: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_restore_error {
+        pub hash: [u8; 32],
+        pub reason: u32,
+        pub pad: u32,
+    }
+
+    pub const BW_RESTORE_OK: u8 = 0;
+    pub const BW_RESTORE_ENOTFOUND: u8 = 16;
+    pub const BW_RESTORE_EMISMATCH: u8 = 17;
+    pub const BW_RESTORE_ENOPACKFILE: u8 = 18;
+    pub const BW_RESTORE_ENOTTREE: u8 = 19;
+    pub const BW_RESTORE_EFORMAT: u8 = 20;
+    pub const BW_RESTORE_SKEW_SLOTS: u32 = 0x100;
+
     /// `fn(user, send, recv, bytes_per_rank)`: deliver `send[r * b ..]` to rank r's `recv[my_rank * b ..]`.
     pub type bw_host_all_to_all =
         Option<unsafe extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes_per_rank: u64) -> c_int>;
@@ -338,6 +384,30 @@ pub mod ffi {
                                packfiles: *const bw_packfile, n_pf: u64, entries: *const bw_unpack_entry, n: u64,
                                flags: u32, dst: *mut u8, dst_off: *const u64, out_len: *mut u64,
                                status: *mut u8) -> c_int;
+
+        // restore: the data path of dir_unpacker.rs:14-130 (locate, tree walk, file assembly)
+        pub fn bw_restore_open(ctx: *mut bw_ctx, prk: *const u8, d_packfiles: *const u8,
+                               packfiles: *const bw_packfile, ids: *const u8, n_pf: u64,
+                               entries: *const bw_unpack_entry, n_entries: u64, index_items: *const u8,
+                               n_items: u64, slots: u32, out: *mut *mut bw_restore) -> c_int;
+        pub fn bw_restore_open_host(ctx: *mut bw_ctx, prk: *const u8, packfiles_data: *const u8,
+                                    packfiles: *const bw_packfile, ids: *const u8, n_pf: u64,
+                                    entries: *const bw_unpack_entry, n_entries: u64, index_items: *const u8,
+                                    n_items: u64, slots: u32, out: *mut *mut bw_restore) -> c_int;
+        pub fn bw_restore_close(session: *mut bw_restore) -> c_int;
+        pub fn bw_restore_locate(session: *mut bw_restore, hashes: *const u8, n: u64, entry_idx: *mut u64,
+                                 status: *mut u8) -> c_int;
+        pub fn bw_restore_trees(session: *mut bw_restore, root_hash: *const u8, flags: u32,
+                                nodes: *mut bw_restore_node, node_cap: u64, names: *mut u8, names_cap: u64,
+                                chunks: *mut u8, chunks_cap: u64, counts: *mut bw_restore_counts,
+                                err: *mut bw_restore_error) -> c_int;
+        pub fn bw_restore_files_device(session: *mut bw_restore, chunks: *const u8, file_first: *const u64,
+                                       n_files: u64, flags: u32, d_dst: *mut u8, dst_cap: u64,
+                                       file_off: *mut u64, file_len: *mut u64, file_status: *mut u8,
+                                       file_bad_child: *mut u64, n_done: *mut u64) -> c_int;
+        pub fn bw_restore_files(session: *mut bw_restore, chunks: *const u8, file_first: *const u64, n_files: u64,
+                                flags: u32, dst: *mut u8, dst_cap: u64, file_off: *mut u64, file_len: *mut u64,
+                                file_status: *mut u8, file_bad_child: *mut u64, n_done: *mut u64) -> c_int;
 
         pub fn bw_profile_enable(ctx: *mut bw_ctx, on: c_int) -> c_int;
         pub fn bw_profile_read(ctx: *mut bw_ctx, stage_ms: *mut f64, n_batches: *mut u64) -> c_int;
