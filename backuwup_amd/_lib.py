@@ -104,6 +104,22 @@ class BwRestoreError(ctypes.Structure):
     _fields_ = [("hash", ctypes.c_uint8 * 32), ("reason", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+class BwPrunePackfileStat(ctypes.Structure):
+    _fields_ = [("live_blobs", ctypes.c_uint64), ("live_bytes", ctypes.c_uint64), ("total_blobs", ctypes.c_uint64),
+                ("total_bytes", ctypes.c_uint64)]
+
+
+class BwPruneCounts(ctypes.Structure):
+    _fields_ = [("live_blobs", ctypes.c_uint64), ("live_bytes", ctypes.c_uint64), ("total_blobs", ctypes.c_uint64),
+                ("total_bytes", ctypes.c_uint64), ("n_trees_expanded", ctypes.c_uint64), ("n_levels", ctypes.c_uint64),
+                ("n_errors", ctypes.c_uint64)]
+
+
+class BwPruneError(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("parent", ctypes.c_uint8 * 32), ("child_pos", ctypes.c_uint64),
+                ("reason", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
 BW_TREE_FILE, BW_TREE_DIR = 0, 1
 BW_TREE_HAS_SIZE, BW_TREE_HAS_MTIME, BW_TREE_HAS_CTIME = 1, 2, 4
 BW_TREE_BLOB_MAX_CHILDREN = 10000
@@ -227,6 +243,14 @@ SIGNATURES = [
                                                u64p, u64p, u8p, u64p, u64p]),
     ("bw_restore_files", ctypes.c_int, [vp, vp, u64p, ctypes.c_uint64, ctypes.c_uint32, vp, ctypes.c_uint64,
                                         u64p, u64p, u8p, u64p, u64p]),
+    ("bw_prune_mark", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, u8p, ctypes.POINTER(BwPrunePackfileStat),
+                                     ctypes.POINTER(BwPruneCounts), ctypes.POINTER(BwPruneError), ctypes.c_uint64]),
+    ("bw_prune_plan", ctypes.c_int, [ctypes.POINTER(BwUnpackEntry), ctypes.c_uint64, ctypes.POINTER(BwPackfile),
+                                     ctypes.c_uint64, u8p, u8p, u64p, ctypes.c_uint64, u64p, ctypes.POINTER(BwPackfile),
+                                     ctypes.c_uint64, u64p, u64p, u64p]),
+    ("bw_prune_repack_device", ctypes.c_int, [vp, u64p, ctypes.c_uint64, ctypes.POINTER(BwPackfile), ctypes.c_uint64, vp,
+                                              vp]),
+    ("bw_prune_repack", ctypes.c_int, [vp, u64p, ctypes.c_uint64, ctypes.POINTER(BwPackfile), ctypes.c_uint64, vp, vp]),
     ("bw_profile_enable", ctypes.c_int, [vp, ctypes.c_int]),
     ("bw_fastcdc_chunks_hashed", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint32, vp, ctypes.c_uint64, u64p, u64p]),

@@ -286,6 +286,10 @@ static uint64_t entry_len(uint64_t sealed, uint64_t section_off) {
     return 32 + 1 + 1 + varint_len(sealed) + varint_len(section_off);
 }
 
+// prune (bw_prune.hip) lays out headers of its own with the same sizes
+uint32_t bw::pack_varint_len(uint64_t v) { return varint_len(v); }
+uint64_t bw::pack_entry_len(uint64_t sealed, uint64_t section_off) { return entry_len(sealed, section_off); }
+
 // write_packfiles' drain (pack.rs:123-148) over queue positions [i, to): packfiles close when their
 // blob section reaches PACKFILE_TARGET_SIZE or PACKFILE_MAX_BLOBS blobs; the last may be a remainder.
 static void plan_range(const uint64_t* payload_len, uint64_t i, uint64_t to, uint32_t flags,

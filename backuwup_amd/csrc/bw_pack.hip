@@ -11,6 +11,9 @@
 //                 form (hash, kind, compression = Zstd, length, offset; filesystem/mod.rs:36-43)
 //                 into the header staging area, and its 12-byte nonce in front of its sealed
 //                 bytes in the packfile.
+//   k_pack_meta_sealed  k_pack_meta for a blob that is already sealed and moves verbatim (prune,
+//                 bw_prune.hip): the entry of a stored bw_unpack_entry with its compression tag
+//                 as stored; the nonce travels with the sealed bytes.
 //   k_pack_files  one lane per packfile: the Vec length varint of the header and the u64 LE
 //                 encrypted-header length that opens the packfile (pack.rs:222-224).
 //   k_index_parse one lane per decrypted index file: the bincode varint Vec length, checked
@@ -51,6 +54,21 @@ __global__ void k_pack_meta(const PackBlob* __restrict__ blobs, uint64_t n, uint
     for (int k = 0; k < 12; k++) q[k] = b.nonce[k];
 }
 
+__global__ void k_pack_meta_sealed(const bw_unpack_entry* __restrict__ entries, const uint64_t* __restrict__ order,
+                                   const uint64_t* __restrict__ sect, const uint64_t* __restrict__ hoff, uint64_t n,
+                                   uint8_t* __restrict__ hdr) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bw_unpack_entry& e = entries[order[i]];
+    uint8_t* p = hdr + hoff[i];
+    for (int k = 0; k < 32; k++) p[k] = e.hash[k];
+    p += 32;
+    p += put_varint(p, e.kind);
+    p += put_varint(p, e.compression);
+    p += put_varint(p, e.length);
+    put_varint(p, sect[i]);
+}
+
 __global__ void k_pack_files(const PackFileDesc* __restrict__ files, uint64_t n, uint8_t* __restrict__ hdr,
                              uint8_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,6 +85,14 @@ void launch_pack_meta(hipStream_t st, const PackBlob* blobs, uint64_t n, const P
     if (n_files)
         hipLaunchKernelGGL(k_pack_files, dim3((unsigned)((n_files + 255) / 256)), dim3(256), 0, st, files, n_files, hdr,
                            out);
+}
+
+// declared in bw_prune.h
+void launch_pack_meta_sealed(hipStream_t st, const bw_unpack_entry* entries, const uint64_t* order, const uint64_t* sect,
+                             const uint64_t* hoff, uint64_t n, uint8_t* hdr) {
+    if (n)
+        hipLaunchKernelGGL(k_pack_meta_sealed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, entries, order, sect, hoff,
+                           n, hdr);
 }
 
 // ------------------------------------------------------------------ index files

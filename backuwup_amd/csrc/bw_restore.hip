@@ -28,64 +28,6 @@ using namespace bw;
 // same key).  Probing is linear from a mix of the key's first 8 bytes and is bounded by the table
 // size; the tables are at most half full.
 
-__device__ static inline uint64_t rs_load8(const uint8_t* p) {
-    uint64_t v = 0;
-    for (int i = 0; i < 8; i++) v |= (uint64_t)p[i] << (8 * i);
-    return v;
-}
-
-__device__ static inline uint32_t rs_mix(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    return (uint32_t)x;
-}
-
-__device__ static inline bool rs_eq(const uint8_t* a, const uint8_t* b, uint32_t n) {
-    uint32_t d = 0;
-    for (uint32_t i = 0; i < n; i++) d |= a[i] ^ b[i];
-    return d == 0;
-}
-
-// keys of `klen` bytes at rec + idx * stride (+ a u32 salt at salt_at, when salt_at != ~0, that
-// must be equal too: the packfile position of a header entry)
-struct RsKeys {
-    const uint8_t* rec;
-    uint32_t stride, klen, salt_at;
-};
-
-__device__ static inline uint32_t rs_salt(const RsKeys& k, uint32_t idx) {
-    if (k.salt_at == ~0u) return 0;
-    uint32_t v;
-    memcpy(&v, k.rec + (uint64_t)idx * k.stride + k.salt_at, 4);
-    return v;
-}
-
-__device__ static void rs_insert(uint32_t* tab, uint32_t cap, const RsKeys& k, uint32_t idx) {
-    const uint8_t* key = k.rec + (uint64_t)idx * k.stride;
-    const uint32_t salt = rs_salt(k, idx);
-    const uint32_t h = rs_mix(rs_load8(key) ^ ((uint64_t)salt << 32));
-    for (uint32_t probe = 0; probe < cap; probe++) {
-        const uint32_t slot = (h + probe) & (cap - 1);
-        uint32_t cur = atomicCAS(&tab[slot], RS_EMPTY, idx);
-        if (cur == RS_EMPTY) return;
-        if (rs_salt(k, cur) == salt && rs_eq(k.rec + (uint64_t)cur * k.stride, key, k.klen)) {
-            atomicMin(&tab[slot], idx);
-            return;
-        }
-    }
-}
-
-__device__ static uint32_t rs_find(const uint32_t* tab, uint32_t cap, const RsKeys& k, const uint8_t* key, uint32_t salt) {
-    const uint32_t h = rs_mix(rs_load8(key) ^ ((uint64_t)salt << 32));
-    for (uint32_t probe = 0; probe < cap; probe++) {
-        const uint32_t cur = tab[(h + probe) & (cap - 1)];
-        if (cur == RS_EMPTY) return RS_EMPTY;
-        if (rs_salt(k, cur) == salt && rs_eq(k.rec + (uint64_t)cur * k.stride, key, k.klen)) return cur;
-    }
-    return RS_EMPTY;
-}
-
 __global__ void k_rs_build_ids(const uint8_t* ids, uint64_t n, uint32_t* tab, uint32_t cap) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -113,24 +55,9 @@ __global__ void k_rs_locate(const uint8_t* hashes, uint64_t n, const uint8_t* it
                             const uint32_t* entry_tab, uint32_t entry_cap, uint64_t* entry_idx, uint8_t* status) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint8_t* key = hashes + 32 * i;
-    uint64_t idx = ~0ull;
-    uint8_t st;
-    const uint32_t item = item_cap ? rs_find(item_tab, item_cap, RsKeys{items, BW_INDEX_ENTRY_BYTES, 32, ~0u}, key, 0) : RS_EMPTY;
-    if (item == RS_EMPTY) {
-        st = BW_RESTORE_ENOTFOUND;
-    } else if (item_pos[item] == RS_EMPTY) {
-        st = BW_RESTORE_ENOPACKFILE;
-    } else {
-        const uint32_t e = entry_cap ? rs_find(entry_tab, entry_cap,
-                                               RsKeys{(const uint8_t*)entries, (uint32_t)sizeof(bw_unpack_entry), 32, 32},
-                                               key, item_pos[item])
-                                     : RS_EMPTY;
-        st = e == RS_EMPTY ? BW_RESTORE_EMISMATCH : BW_RESTORE_OK;
-        if (e != RS_EMPTY) idx = e;
-    }
+    uint64_t idx;
+    status[i] = rs_locate_one(RsLocator{items, item_tab, item_pos, entries, entry_tab, item_cap, entry_cap}, hashes + 32 * i, idx);
     entry_idx[i] = idx;
-    status[i] = st;
 }
 
 static dim3 rs_grid(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
@@ -327,8 +254,6 @@ void bw::launch_rs_scan(hipStream_t st, const RsInst* inst, uint64_t n, const ui
     hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, st, inst, n, slot_len, run, dst_off, piece0);
 }
 
-typedef uint32_t rs_u4 __attribute__((ext_vector_type(4)));
-
 // k_rs_gather: every instance's blob copied from its decode slot to its place in its file.  A wave
 // takes one piece (RS_PIECE bytes of one instance, found by a binary search of the piece prefix), so
 // a 3 MiB chunk is 96 waves' work and a chunk of a few KiB one wave's.  Source and destination start
@@ -362,37 +287,7 @@ __global__ void __launch_bounds__(256) k_rs_gather(const RsInst* inst, uint64_t 
         const uint64_t nb = len - p0 < RS_PIECE ? len - p0 : RS_PIECE;
         const uint8_t* s = slots + slot_off[slot] + p0;
         uint8_t* d = dst + d_at + p0;
-        const uint64_t to16 = (16 - ((uintptr_t)d & 15)) & 15, head = to16 < nb ? to16 : nb;
-        if (lane < head) d[lane] = s[lane];
-        const uint64_t nvec = (nb - head) / 16;
-        const uint8_t* sv = s + head;
-        rs_u4* dv = (rs_u4*)(d + head);
-        const uint32_t sh = (uint32_t)((uintptr_t)sv & 15);
-        if (sh == 0) {
-            const rs_u4* av = (const rs_u4*)sv;
-            for (uint64_t v = lane; v < nvec; v += 64) dv[v] = av[v];
-        } else {
-            const rs_u4* av = (const rs_u4*)(sv - sh);
-            const uint32_t q = sh >> 2, r = sh & 3;
-            for (uint64_t v = lane; v < nvec; v += 64) {
-                const rs_u4 a = av[v], b = av[v + 1];
-                // the five dwords the 16 bytes lie in: dwords q .. q + 4 of the eight loaded, picked by
-                // selects (two levels of v_cndmask on q's bits), not by branches
-                const bool q1 = q & 1, q2 = q & 2;
-                const uint32_t e0 = q1 ? a.y : a.x, e1 = q1 ? a.z : a.y, e2 = q1 ? a.w : a.z, e3 = q1 ? b.x : a.w,
-                               e4 = q1 ? b.y : b.x, e5 = q1 ? b.z : b.y, e6 = q1 ? b.w : b.z;
-                const uint32_t w0 = q2 ? e2 : e0, w1 = q2 ? e3 : e1, w2 = q2 ? e4 : e2, w3 = q2 ? e5 : e3,
-                               w4 = q2 ? e6 : e4;
-                rs_u4 o;
-                o.x = __builtin_amdgcn_alignbyte(w1, w0, r);
-                o.y = __builtin_amdgcn_alignbyte(w2, w1, r);
-                o.z = __builtin_amdgcn_alignbyte(w3, w2, r);
-                o.w = __builtin_amdgcn_alignbyte(w4, w3, r);
-                dv[v] = o;
-            }
-        }
-        const uint64_t done = head + 16 * nvec;
-        if (lane < nb - done) d[done + lane] = s[done + lane];
+        rs_copy_piece<false>(s, d, nb, lane);
     }
 }
 
@@ -407,25 +302,6 @@ void bw::launch_rs_gather(hipStream_t st, const RsInst* inst, uint64_t n, const 
 }
 
 // ------------------------------------------------------------------ the session
-struct bw_restore {
-    bw_ctx* c = nullptr;
-    uint8_t prk[32];
-    const uint8_t* d_pf = nullptr;
-    std::vector<bw_packfile> pf;
-    std::vector<bw_unpack_entry> entries;
-    uint64_t n_items = 0;
-    uint32_t slots = 0;
-    uint32_t id_cap = 0, item_cap = 0, entry_cap = 0;
-    DevBuf ids, items, d_entries, id_tab, item_tab, item_pos, entry_tab;
-    DevBuf slot_buf;  // slots x RS_SLOT_STRIDE
-    DevBuf q;         // locate: [entry_idx | hashes | status]
-    DevBuf tab;       // a sub-batch's tables
-    DevBuf run;       // the gather's running output offset
-    DevBuf emit;      // the parser's packed names and children rows
-    DevBuf win;       // bw_restore_files' window
-    DevBuf pf_buf;    // bw_restore_open_host: the packfiles
-};
-
 namespace {
 struct HashKey {
     std::array<uint8_t, 32> h;
@@ -459,7 +335,8 @@ extern "C" int bw_restore_close(bw_restore* s) {
     hipSetDevice(s->c->device);
     hipStreamSynchronize(s->c->stream);
     for (DevBuf* b : {&s->ids, &s->items, &s->d_entries, &s->id_tab, &s->item_tab, &s->item_pos, &s->entry_tab, &s->slot_buf,
-                      &s->q, &s->tab, &s->run, &s->emit, &s->win, &s->pf_buf})
+                      &s->q, &s->tab, &s->run, &s->emit, &s->win, &s->pf_buf, &s->pr_bits, &s->pr_front[0],
+                      &s->pr_front[1], &s->pr_ctr, &s->pr_err, &s->pr_stat, &s->pr_tab, &s->pr_hdr})
         free_dev(*b);
     delete s;
     return BW_OK;
@@ -577,14 +454,7 @@ extern "C" int bw_restore_locate(bw_restore* s, const uint8_t* hashes, uint64_t 
     return rs_locate(s, hashes, n, entry_idx, status);
 }
 
-// A sub-batch's device tables, carved from s->tab: per slot its length, offset and scratch, per
-// instance its record, destination and piece prefix.
-struct RsTables {
-    uint64_t *slot_len, *slot_off, *map, *dst_off, *piece0;
-    RsInst* inst;
-};
-
-static int rs_tables(bw_restore* s, uint64_t m, uint64_t ni, RsTables& t) {
+int bw::rs_tables(bw_restore* s, uint64_t m, uint64_t ni, RsTables& t) {
     if (int rc = ensure(s->c, s->tab, 24 * m + 24 * ni + 64)) return rc;
     uint64_t* p = P<uint64_t>(s->tab);
     t.slot_len = p;
@@ -598,7 +468,7 @@ static int rs_tables(bw_restore* s, uint64_t m, uint64_t ni, RsTables& t) {
 
 // m located blobs (entry indices eidx) opened and decoded into the slots at off[k]; sizes on the
 // device in t.slot_len, and with the statuses on the host
-static int rs_decode(bw_restore* s, const std::vector<uint64_t>& eidx, const std::vector<uint64_t>& off, uint32_t flags,
+int bw::rs_decode(bw_restore* s, const std::vector<uint64_t>& eidx, const std::vector<uint64_t>& off, uint32_t flags,
                      const RsTables& t, std::vector<uint64_t>& out_len, std::vector<uint8_t>& st) {
     const uint64_t m = eidx.size();
     out_len.assign(m, 0);

@@ -554,6 +554,95 @@ private:
     bw_restore* s_ = nullptr;
 };
 
+// ------------------------------------------------------------------ prune (no counterpart in the reference)
+// Over an open Restore: mark() = which header entries the kept roots reach, plan() = the live entries
+// of the packfiles worth rewriting and their new grouping, repack() = the new packfiles, the moved
+// blobs copied sealed as they are.
+class Prune {
+public:
+    struct Mark {
+        std::vector<uint8_t> live;                  // one byte per header entry
+        std::vector<bw_prune_packfile_stat> stats;  // per packfile
+        bw_prune_counts counts{};
+        std::vector<bw_prune_error> errors;         // in no particular order
+    };
+    struct Plan {
+        std::vector<uint64_t> order;    // the moved entries
+        std::vector<bw_packfile> plan;  // the new packfiles over them
+        uint64_t total_bytes = 0;
+    };
+
+    Prune(Context& ctx, Restore& session, const PackfileTable& t, const std::vector<bw_unpack_entry>& entries)
+        : ctx_(ctx), s_(session), t_(t), entries_(entries) {}
+
+    Mark mark(const std::vector<BlobHash>& roots, bool verify = false) {
+        Mark m;
+        m.live.resize(entries_.size() + 1);
+        m.stats.resize(t_.tab.size() + 1);
+        std::vector<uint8_t> r;
+        for (const auto& x : roots) r.insert(r.end(), x.begin(), x.end());
+        uint64_t cap = 64;
+        for (;;) {
+            m.errors.resize(cap + 1);
+            const int rc = bw_prune_mark(s_.get(), r.data(), roots.size(), verify ? BW_UNPACK_VERIFY : 0, m.live.data(),
+                                         m.stats.data(), &m.counts, m.errors.data(), cap);
+            if (rc != BW_ENOSPC) {
+                check(rc, ctx_.get());
+                break;
+            }
+            cap = m.counts.n_errors;
+        }
+        m.live.resize(entries_.size());
+        m.stats.resize(t_.tab.size());
+        m.errors.resize(m.counts.n_errors);
+        return m;
+    }
+
+    // a packfile is rewritten when dead_bytes / total_bytes exceeds the threshold
+    static std::vector<uint8_t> choose_rewrite(const std::vector<bw_prune_packfile_stat>& stats, double max_dead_fraction = 0.0) {
+        std::vector<uint8_t> rw(stats.size());
+        for (size_t p = 0; p < stats.size(); p++)
+            rw[p] = stats[p].total_bytes && (double)(stats[p].total_bytes - stats[p].live_bytes) > max_dead_fraction * (double)stats[p].total_bytes;
+        return rw;
+    }
+
+    Plan plan(const std::vector<uint8_t>& live, const std::vector<uint8_t>& rewrite) {
+        Plan p;
+        uint64_t nm = 0, nn = 0, bad = 0;
+        int rc = bw_prune_plan(entries_.data(), entries_.size(), t_.tab.data(), t_.tab.size(), live.data(), rewrite.data(),
+                               nullptr, 0, &nm, nullptr, 0, &nn, &p.total_bytes, &bad);
+        if (rc != BW_ENOSPC) check(rc, ctx_.get());
+        p.order.resize(nm + 1);
+        p.plan.resize(nn + 1);
+        check(bw_prune_plan(entries_.data(), entries_.size(), t_.tab.data(), t_.tab.size(), live.data(), rewrite.data(),
+                            p.order.data(), nm, &nm, p.plan.data(), nn, &nn, &p.total_bytes, &bad),
+              ctx_.get());
+        p.order.resize(nm);
+        p.plan.resize(nn);
+        return p;
+    }
+
+    // (id, bytes) per new packfile; new_ids: at least one per planned packfile
+    std::vector<std::pair<PackfileId, std::vector<uint8_t>>> repack(const Plan& p, const std::vector<PackfileId>& new_ids) {
+        if (new_ids.size() < p.plan.size()) throw Error(BW_EINVAL, "prune: too few new packfile ids");
+        std::vector<uint8_t> ids, out(p.total_bytes + 1);
+        for (size_t g = 0; g < p.plan.size(); g++) ids.insert(ids.end(), new_ids[g].begin(), new_ids[g].end());
+        check(bw_prune_repack(s_.get(), p.order.data(), p.order.size(), p.plan.data(), p.plan.size(), ids.data(), out.data()),
+              ctx_.get());
+        std::vector<std::pair<PackfileId, std::vector<uint8_t>>> res;
+        for (size_t g = 0; g < p.plan.size(); g++)
+            res.emplace_back(new_ids[g], std::vector<uint8_t>(out.begin() + p.plan[g].offset,
+                                                              out.begin() + p.plan[g].offset + p.plan[g].size));
+        return res;
+    }
+
+private:
+    Context& ctx_;
+    Restore& s_;
+    const PackfileTable& t_;
+    const std::vector<bw_unpack_entry>& entries_;
+};
+
 // ------------------------------------------------------------------ index files (blob_index.rs)
 using IndexEntry = std::pair<BlobHash, PackfileId>;
 

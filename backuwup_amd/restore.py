@@ -64,6 +64,7 @@ class Session:
                                                en.ctypes.data_as(ctypes.POINTER(_lib.BwUnpackEntry)), en.size,
                                                _ptr(items), items.shape[0], slots, ctypes.byref(h)), ctx.h)
         self.h = h
+        self.n_entries, self.n_packfiles = int(en.size), int(pl.size if plan is not None else len(blobs))
 
     def close(self):
         if getattr(self, "h", None):

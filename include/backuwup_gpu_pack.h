@@ -368,6 +368,78 @@ int bw_restore_files(bw_restore* session, const uint8_t* chunks, const uint64_t*
                      uint32_t flags, uint8_t* dst, uint64_t dst_cap, uint64_t* file_off, uint64_t* file_len,
                      uint8_t* file_status, uint64_t* file_bad_child, uint64_t* n_done);
 
+/* ---- prune: which header entries a set of roots reaches, and packfiles of the live ones ----
+ * The reference has no prune; this goes past it as BW_UNPACK_VERIFY does.  Three steps over an open
+ * restore session: bw_prune_mark (device), bw_prune_plan (host), bw_prune_repack (device).  A sealed
+ * blob is nonce || AES-GCM(derive_backup_key(hash), nonce)(frame): neither depends on the packfile,
+ * so a repack copies blobs verbatim and seals only new headers.  All calls are synchronous. */
+typedef struct bw_prune_packfile_stat {
+    uint64_t live_blobs, live_bytes, total_blobs, total_bytes; /* bytes: 12 + length per entry */
+} bw_prune_packfile_stat;
+typedef struct bw_prune_counts {
+    uint64_t live_blobs, live_bytes, total_blobs, total_bytes; /* the sums of the per-packfile stats   */
+    uint64_t n_trees_expanded; /* tree blobs opened, parsed and expanded                                */
+    uint64_t n_levels;         /* rounds of the walk (a next_sibling is one step, like a child)         */
+    uint64_t n_errors;         /* always the full number                                                */
+} bw_prune_counts;
+/* A reference error names the reference: hash = the hash referred to, parent = the piece that holds
+ * it (all zero for a root), child_pos = the child's position (~0 for next_sibling, the root's index
+ * for a root).  An entry error names an entry: hash = the entry's, parent zero, child_pos = ~0. */
+typedef struct bw_prune_error {
+    uint8_t hash[32];
+    uint8_t parent[32];
+    uint64_t child_pos;
+    uint32_t reason; /* BW_RESTORE_* or BW_UNPACK_* */
+    uint32_t pad;
+} bw_prune_error;
+
+/* Reachability from n_roots root hashes (host, 32 B each; 0 roots: everything is dead) over the
+ * session's entries.  live[e] (host, one byte per session entry) = 1 when a kept root reaches entry
+ * e.  The walk is level-synchronous: a frontier of tree entries not yet expanded (a device list)
+ * goes through the unpack chain `slots` blobs at a time, is parsed in the slots, and one kernel
+ * resolves every children row and next_sibling with the session's tables (the answer
+ * bw_restore_locate gives), sets the entry's live bit and, for a tree reference (a child of a Dir
+ * piece, a next_sibling, a root), its queued bit; the lane that sets the queued bit appends the
+ * entry to the next frontier.  Each distinct tree blob is expanded once whatever the number of
+ * roots and paths that reach it; cycles end by themselves and are no error.  The children of a File
+ * piece are marked whatever their kind and never opened.  A hash held by several entries marks only
+ * the entry bw_restore_locate resolves it to.  flags: BW_UNPACK_VERIFY (tree blobs are re-hashed;
+ * chunk payloads are never read) or 0.
+ * Errors never stop the walk.  Reference errors: a failed locate (BW_RESTORE_ENOTFOUND, _EMISMATCH,
+ * _ENOPACKFILE), or a tree reference that resolves to a FileChunk entry (BW_RESTORE_ENOTTREE; the
+ * entry is marked live all the same).  Entry errors: a tree blob the chain or the parser refuses
+ * (BW_UNPACK_ETAG, _EZSTD, _EDIGEST, _ERANGE, BW_RESTORE_EFORMAT; it is live but not expanded), and a
+ * live FileChunk entry whose nonce + length leaves its packfile or whose length < 16
+ * (BW_UNPACK_ERANGE), each reported once.  errs is filled in no particular order;
+ * counts->n_errors > err_cap -> BW_ENOSPC with live, stats (n_pf records) and counts still filled. */
+int bw_prune_mark(bw_restore* session, const uint8_t* roots, uint64_t n_roots, uint32_t flags, uint8_t* live,
+                  bw_prune_packfile_stat* stats, bw_prune_counts* counts, bw_prune_error* errs, uint64_t err_cap);
+
+/* Host only.  order = the live entries of the packfiles with rewrite[p] != 0, ascending by packfile
+ * position, then by entry index; plan = write_packfiles' grouping over their sealed lengths (the
+ * rule of bw_pack_plan with flags 0: first_blob counts positions of order, sizes include the exact
+ * header).  Packfiles with rewrite[p] == 0 are left alone, dead blobs and all; a rewritten packfile
+ * without a live blob contributes nothing.  A live entry of a rewritten packfile whose range leaves
+ * its packfile or whose length < 16 -> BW_EINVAL with *bad_entry = its index (else ~0); a new
+ * packfile above BW_PACKFILE_MAX_SIZE -> BW_EINVAL.  A cap too small -> BW_ENOSPC with *n_moved,
+ * *n_new and *total_bytes set. */
+int bw_prune_plan(const bw_unpack_entry* entries, uint64_t n_entries, const bw_packfile* packfiles, uint64_t n_pf,
+                  const uint8_t* live, const uint8_t* rewrite, uint64_t* order, uint64_t order_cap, uint64_t* n_moved,
+                  bw_packfile* plan, uint64_t plan_cap, uint64_t* n_new, uint64_t* total_bytes, uint64_t* bad_entry);
+
+/* The planned packfiles into d_out (device, plan's total_bytes): each moved blob's nonce || sealed
+ * bytes copied from the session's packfiles by one kernel (no blob is opened), each header built
+ * from the moved entries (hash, kind, length and the compression tag exactly as stored; offset = the
+ * running 12 + length sum) and sealed with key "header" and nonce new_ids[12 p ..].  order and plan
+ * are checked again against the session's entries: BW_EINVAL when they do not match.  Nothing
+ * outside [d_out, d_out + total_bytes) is written and no packfile byte outside the moved blobs is
+ * read.  d_out must not overlap the session's packfiles. */
+int bw_prune_repack_device(bw_restore* session, const uint64_t* order, uint64_t n_moved, const bw_packfile* plan,
+                           uint64_t n_new, const uint8_t* new_ids, uint8_t* d_out);
+/* Same into a host buffer. */
+int bw_prune_repack(bw_restore* session, const uint64_t* order, uint64_t n_moved, const bw_packfile* plan,
+                    uint64_t n_new, const uint8_t* new_ids, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

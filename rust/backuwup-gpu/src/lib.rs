@@ -209,6 +209,37 @@ pub mod ffi {
         pub pad: u32,
     }
 
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_prune_packfile_stat {
+        pub live_blobs: u64,
+        pub live_bytes: u64,
+        pub total_blobs: u64,
+        pub total_bytes: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_prune_counts {
+        pub live_blobs: u64,
+        pub live_bytes: u64,
+        pub total_blobs: u64,
+        pub total_bytes: u64,
+        pub n_trees_expanded: u64,
+        pub n_levels: u64,
+        pub n_errors: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_prune_error {
+        pub hash: [u8; 32],
+        pub parent: [u8; 32],
+        pub child_pos: u64,
+        pub reason: u32,
+        pub pad: u32,
+    }
+
     pub const BW_RESTORE_OK: u8 = 0;
     pub const BW_RESTORE_ENOTFOUND: u8 = 16;
     pub const BW_RESTORE_EMISMATCH: u8 = 17;
@@ -408,6 +439,18 @@ pub mod ffi {
         pub fn bw_restore_files(session: *mut bw_restore, chunks: *const u8, file_first: *const u64, n_files: u64,
                                 flags: u32, dst: *mut u8, dst_cap: u64, file_off: *mut u64, file_len: *mut u64,
                                 file_status: *mut u8, file_bad_child: *mut u64, n_done: *mut u64) -> c_int;
+
+        pub fn bw_prune_mark(session: *mut bw_restore, roots: *const u8, n_roots: u64, flags: u32, live: *mut u8,
+                             stats: *mut bw_prune_packfile_stat, counts: *mut bw_prune_counts,
+                             errs: *mut bw_prune_error, err_cap: u64) -> c_int;
+        pub fn bw_prune_plan(entries: *const bw_unpack_entry, n_entries: u64, packfiles: *const bw_packfile, n_pf: u64,
+                             live: *const u8, rewrite: *const u8, order: *mut u64, order_cap: u64, n_moved: *mut u64,
+                             plan: *mut bw_packfile, plan_cap: u64, n_new: *mut u64, total_bytes: *mut u64,
+                             bad_entry: *mut u64) -> c_int;
+        pub fn bw_prune_repack_device(session: *mut bw_restore, order: *const u64, n_moved: u64,
+                                      plan: *const bw_packfile, n_new: u64, new_ids: *const u8, d_out: *mut u8) -> c_int;
+        pub fn bw_prune_repack(session: *mut bw_restore, order: *const u64, n_moved: u64, plan: *const bw_packfile,
+                               n_new: u64, new_ids: *const u8, out: *mut u8) -> c_int;
 
         pub fn bw_profile_enable(ctx: *mut bw_ctx, on: c_int) -> c_int;
         pub fn bw_profile_read(ctx: *mut bw_ctx, stage_ms: *mut f64, n_batches: *mut u64) -> c_int;
