@@ -120,6 +120,25 @@ class BwPruneError(ctypes.Structure):
                 ("reason", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+BW_CHECK_E_RANGE, BW_CHECK_E_ORDER, BW_CHECK_E_UNINDEXED, BW_CHECK_E_SHADOWED = 1, 2, 4, 8
+BW_CHECK_SKIPPED, BW_CHECK_IDUPLICATE = 32, 33
+BW_CHECK_AUTH, BW_CHECK_FULL = 1, 2
+
+
+class BwCheckPackfileStat(ctypes.Structure):
+    _fields_ = [("n_entries", ctypes.c_uint64), ("n_range", ctypes.c_uint64), ("n_order", ctypes.c_uint64),
+                ("n_unindexed", ctypes.c_uint64), ("n_shadowed", ctypes.c_uint64), ("claimed_bytes", ctypes.c_uint64),
+                ("section_bytes", ctypes.c_uint64), ("tail", ctypes.c_int64)]
+
+
+class BwCheckCounts(ctypes.Structure):
+    _fields_ = [("n_entries", ctypes.c_uint64), ("n_range", ctypes.c_uint64), ("n_order", ctypes.c_uint64),
+                ("n_unindexed", ctypes.c_uint64), ("n_shadowed", ctypes.c_uint64), ("claimed_bytes", ctypes.c_uint64),
+                ("section_bytes", ctypes.c_uint64), ("n_items_ok", ctypes.c_uint64), ("n_items_nopackfile", ctypes.c_uint64),
+                ("n_items_mismatch", ctypes.c_uint64), ("n_items_duplicate", ctypes.c_uint64),
+                ("n_packfiles_clean", ctypes.c_uint64)]
+
+
 BW_TREE_FILE, BW_TREE_DIR = 0, 1
 BW_TREE_HAS_SIZE, BW_TREE_HAS_MTIME, BW_TREE_HAS_CTIME = 1, 2, 4
 BW_TREE_BLOB_MAX_CHILDREN = 10000
@@ -251,6 +270,11 @@ SIGNATURES = [
     ("bw_prune_repack_device", ctypes.c_int, [vp, u64p, ctypes.c_uint64, ctypes.POINTER(BwPackfile), ctypes.c_uint64, vp,
                                               vp]),
     ("bw_prune_repack", ctypes.c_int, [vp, u64p, ctypes.c_uint64, ctypes.POINTER(BwPackfile), ctypes.c_uint64, vp, vp]),
+    ("bw_auth_device", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
+    ("bw_auth", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
+    ("bw_check_structure", ctypes.c_int, [vp, u8p, u8p, ctypes.POINTER(BwCheckPackfileStat),
+                                          ctypes.POINTER(BwCheckCounts)]),
+    ("bw_check_data", ctypes.c_int, [vp, ctypes.c_uint32, u8p, u8p]),
     ("bw_profile_enable", ctypes.c_int, [vp, ctypes.c_int]),
     ("bw_fastcdc_chunks_hashed", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint32, vp, ctypes.c_uint64, u64p, u64p]),

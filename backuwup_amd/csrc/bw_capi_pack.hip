@@ -18,6 +18,7 @@
 #include "../../include/backuwup_gpu.h"
 #include "bw_device.h"
 #include "bw_internal.h"
+#include "bw_seal.h"
 #include "bw_ctx.h"
 #include "bw_unpack.h"
 #include "bw_restore.h"
@@ -30,12 +31,14 @@ using namespace bw;
 
 // raw_len (sealing only, may be null): item i's plaintext is the zstd store frame of raw_len[i]
 // source bytes at d_src + src_off[i], built inside k_seal_ctr; src_len[i] is the frame length.
+// auth (with dec): the tags are checked and no plaintext is written; d_dst and dst_off are not used.
 static int seal_submit(bw_ctx* c, bool dec, const uint8_t* prk, const uint8_t* d_src, const uint64_t* src_off,
                        const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
                        const uint8_t* nonces, uint8_t* d_dst, const uint64_t* dst_off, uint8_t* ok,
-                       const uint64_t* raw_len = nullptr) {
+                       const uint64_t* raw_len = nullptr, bool auth = false) {
     if (!c || !prk || info_len > BW_SEAL_MAX_INFO) return BW_EINVAL;
-    if (n && (!d_src || !src_off || !src_len || !nonces || !d_dst || !dst_off || (info_len && !info))) return BW_EINVAL;
+    if (n && (!d_src || !src_off || !src_len || !nonces || (info_len && !info))) return BW_EINVAL;
+    if (n && !auth && (!d_dst || !dst_off)) return BW_EINVAL;
     if (dec && n && !ok) return BW_EINVAL;
     hipSetDevice(c->device);
     if (!n) return BW_OK;
@@ -59,7 +62,7 @@ static int seal_submit(bw_ctx* c, bool dec, const uint8_t* prk, const uint8_t* d
     parallel_ranges(n, [&](uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; i++) {
             const uint64_t len = dec ? src_len[i] - 16 : src_len[i];
-            seal_fill_item(&it[i], src_off[i], len, dst_off[i], piece0[i], nonces + 12 * i,
+            seal_fill_item(&it[i], src_off[i], len, auth ? 0 : dst_off[i], piece0[i], nonces + 12 * i,
                            info + (uint64_t)info_len * i, info_len);
             if (raw_len) {
                 it[i].raw_len = (uint32_t)raw_len[i];
@@ -79,7 +82,7 @@ static int seal_submit(bw_ctx* c, bool dec, const uint8_t* prk, const uint8_t* d
     seal_pads(prk, &pads);
     launch_seal(c->stream, dec, raw_len != nullptr, d_src, d_dst, P<SealItem>(c->seal_items), n, pads,
                 P<SealKey>(c->seal_keys), pieces,
-                P<uint32_t>(c->seal_parts), dec ? P<uint8_t>(c->seal_ok) : nullptr);
+                P<uint32_t>(c->seal_parts), dec ? P<uint8_t>(c->seal_ok) : nullptr, auth);
     HIPCHK(c, hipGetLastError());
     if (dec) {
         HIPCHK(c, hipMemcpyAsync(ok, c->seal_ok.p, n, hipMemcpyDeviceToHost, c->stream));
@@ -98,6 +101,29 @@ extern "C" int bw_open_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d
                               const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
                               const uint8_t* nonces, uint8_t* d_dst, const uint64_t* dst_off, uint8_t* ok) {
     return seal_submit(c, true, prk, d_src, src_off, src_len, n, info, info_len, nonces, d_dst, dst_off, ok);
+}
+
+// bw_open_device's verdicts without its plaintext: k_seal_auth recomputes each tag from the ciphertext
+extern "C" int bw_auth_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
+                              const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                              const uint8_t* nonces, uint8_t* ok) {
+    return seal_submit(c, true, prk, d_src, src_off, src_len, n, info, info_len, nonces, nullptr, nullptr, ok, nullptr, true);
+}
+
+// the source is uploaded; nothing but ok comes back
+extern "C" int bw_auth(bw_ctx* c, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
+                       const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len, const uint8_t* nonces,
+                       uint8_t* ok) {
+    if (!c || !prk || (n && (!src || !src_off || !src_len))) return BW_EINVAL;
+    hipSetDevice(c->device);
+    uint64_t s_end = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (src_len[i] < 16) return BW_EINVAL;
+        s_end = std::max(s_end, src_off[i] + src_len[i]);
+    }
+    if (int rc = ensure(c, c->seal_io, s_end + 16)) return rc;
+    if (s_end) HIPCHK(c, hipMemcpyAsync(c->seal_io.p, src, s_end, hipMemcpyHostToDevice, c->stream));
+    return bw_auth_device(c, prk, P<uint8_t>(c->seal_io), src_off, src_len, n, info, info_len, nonces, ok);
 }
 
 // Host-buffer forms: both buffers go through one device staging area ([src | dst]).
@@ -958,8 +984,7 @@ int bw::unpack_blobs_core(bw_ctx* c, const uint8_t* prk, const uint8_t* d_pf, co
         const bw_packfile& f = pf[e.packfile];
         out_len[i] = 0;
         const uint64_t base = 8 + f.header_len;
-        if (base > f.size || e.offset > f.size - base || BW_BLOB_NONCE_SIZE > f.size - base - e.offset ||
-            e.length > f.size - base - e.offset - BW_BLOB_NONCE_SIZE || e.length < BW_SEAL_TAG_BYTES) {
+        if (!rs_range_ok(f.size, f.header_len, e.offset, e.length)) {
             status[i] = BW_UNPACK_ERANGE;
             continue;
         }

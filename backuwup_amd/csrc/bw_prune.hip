@@ -20,14 +20,6 @@
 using namespace bw;
 
 // ------------------------------------------------------------------ the mark
-// nonce + sealed bytes inside the packfile's blob section, and a tag's worth of sealed bytes: the
-// host's check in unpack_blobs_core (BW_UNPACK_ERANGE)
-__host__ __device__ static inline bool pr_range_ok(uint64_t size, uint64_t header_len, uint64_t offset, uint64_t length) {
-    const uint64_t base = 8 + header_len;
-    return !(base > size || offset > size - base || BW_BLOB_NONCE_SIZE > size - base - offset ||
-             length > size - base - offset - BW_BLOB_NONCE_SIZE || length < BW_SEAL_TAG_BYTES);
-}
-
 __device__ static void pr_error(const PrWalk& w, const uint8_t* hash, const uint8_t* parent, uint64_t child_pos,
                                 uint32_t reason) {
     const uint64_t at = atomicAdd((unsigned long long*)&w.ctr[PR_C_ERRORS], 1ull);
@@ -62,7 +54,7 @@ __device__ static void pr_visit(const PrWalk& w, bool active, const uint8_t* key
             if (tree_ref && !tree) pr_error(w, key, parent, child_pos, BW_RESTORE_ENOTTREE);
             // a chunk is never opened here: its range is checked once, by the lane that marks it
             if (!tree && !(old & (PR_LIVE << sh)) &&
-                !pr_range_ok(w.pf[en.packfile].size, w.pf[en.packfile].header_len, en.offset, en.length))
+                !rs_range_ok(w.pf[en.packfile].size, w.pf[en.packfile].header_len, en.offset, en.length))
                 pr_error(w, en.hash, nullptr, ~0ull, BW_UNPACK_ERANGE);
             push = (want & (PR_QUEUED << sh)) && !(old & (PR_QUEUED << sh));
         }
@@ -340,7 +332,7 @@ extern "C" int bw_prune_plan(const bw_unpack_entry* entries, uint64_t n_entries,
             return BW_EINVAL;
         }
         if (!live[i] || !rewrite[e.packfile]) continue;
-        if (!pr_range_ok(packfiles[e.packfile].size, packfiles[e.packfile].header_len, e.offset, e.length)) {
+        if (!rs_range_ok(packfiles[e.packfile].size, packfiles[e.packfile].header_len, e.offset, e.length)) {
             *bad_entry = i;
             return BW_EINVAL;
         }
@@ -406,7 +398,7 @@ extern "C" int bw_prune_repack_device(bw_restore* s, const uint64_t* order, uint
     for (uint64_t i = 0; i < n; i++) {
         if (order[i] >= n_e) return refuse("entry " + std::to_string(i) + " of the order is outside the table");
         const bw_unpack_entry& e = s->entries[order[i]];
-        if (!pr_range_ok(s->pf[e.packfile].size, s->pf[e.packfile].header_len, e.offset, e.length))
+        if (!rs_range_ok(s->pf[e.packfile].size, s->pf[e.packfile].header_len, e.offset, e.length))
             return refuse("entry " + std::to_string(order[i]) + " leaves its packfile");
         if (i) {
             const bw_unpack_entry& q = s->entries[order[i - 1]];

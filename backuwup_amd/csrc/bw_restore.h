@@ -37,7 +37,15 @@ struct RsInst {
 };
 
 
-// ------------------------------------------------------------------ device code shared with bw_prune.hip
+// BW_UNPACK_ERANGE, the one statement of it (the unpack chain, prune's mark and plan, check): the
+// entry's nonce + sealed bytes lie inside the packfile's blob section, and the sealed bytes hold a tag
+__host__ __device__ static inline bool rs_range_ok(uint64_t size, uint64_t header_len, uint64_t offset, uint64_t length) {
+    const uint64_t base = 8 + header_len;
+    return !(base > size || offset > size - base || BW_BLOB_NONCE_SIZE > size - base - offset ||
+             length > size - base - offset - BW_BLOB_NONCE_SIZE || length < BW_SEAL_TAG_BYTES);
+}
+
+// ------------------------------------------------------------------ device code shared with bw_prune.hip and bw_check.hip
 // The locator's probes (the tables are described in bw_restore.hip) and the body of the piece copy.
 __device__ static inline uint64_t rs_load8(const uint8_t* p) {
     uint64_t v = 0;
@@ -237,4 +245,5 @@ struct bw_restore {
     DevBuf win;       // bw_restore_files' window
     DevBuf pf_buf;    // bw_restore_open_host: the packfiles
     DevBuf pr_bits, pr_front[2], pr_ctr, pr_err, pr_stat, pr_tab, pr_hdr;  // prune (bw_prune.hip)
+    DevBuf ck_buf;  // check (bw_check.hip)
 };

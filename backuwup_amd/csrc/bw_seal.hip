@@ -30,7 +30,9 @@
 // folded in.
 #include "bw_device.h"
 #include "bw_internal.h"
+#include "bw_seal.h"
 
+#include <stdlib.h>
 #include <string.h>
 
 namespace bw {
@@ -380,8 +382,10 @@ __device__ __forceinline__ G4 crypt_block(const uint8_t* s, uint8_t* d, uint64_t
     return {c[0], c[1], c[2], c[3]};
 }
 
-// Z = X * H^64 with this wave's 8-bit table: Horner over the bytes of X from the last
-__device__ __forceinline__ G4 gmul_h64(const SealLds& L, G4 x, uint32_t wid) {
+// Z = X * H^64 with this wave's 8-bit table: Horner over the bytes of X from the last.  LT: SealLds
+// or AuthLds (the GHASH tables gt, g4, r8, r4 have the same shape in both).
+template <typename LT>
+__device__ __forceinline__ G4 gmul_h64(const LT& L, G4 x, uint32_t wid) {
     const uint8_t* gbase = (const uint8_t*)&L.gt[wid][0][0];
     const uint32_t xw[4] = {x.w0, x.w1, x.w2, x.w3};
     G4 z = {0, 0, 0, 0};
@@ -402,7 +406,8 @@ __device__ __forceinline__ G4 gmul_h64(const SealLds& L, G4 x, uint32_t wid) {
 }
 
 // Z = X * T with a 4-bit table (16 entries)
-__device__ __forceinline__ G4 gmul_t4(const SealLds& L, G4 x, const uint32_t (*t)[4]) {
+template <typename LT>
+__device__ __forceinline__ G4 gmul_t4(const LT& L, G4 x, const uint32_t (*t)[4]) {
     const uint32_t xw[4] = {x.w0, x.w1, x.w2, x.w3};
     G4 z = {0, 0, 0, 0};
 #pragma unroll
@@ -424,6 +429,50 @@ __device__ __forceinline__ G4 gmul_t4(const SealLds& L, G4 x, const uint32_t (*t
 __device__ __forceinline__ G4 shfl_down4(G4 v, int d) {
     return {(uint32_t)__shfl_down((int)v.w0, d, 64), (uint32_t)__shfl_down((int)v.w1, d, 64),
             (uint32_t)__shfl_down((int)v.w2, d, 64), (uint32_t)__shfl_down((int)v.w3, d, 64)};
+}
+
+// wave wid's tables for the item of K: 8-bit Shoup table of H^64 (4 entries per lane), 4-bit tables
+// of H^(2^k); visible to the whole wave on return
+template <typename LT>
+__device__ __forceinline__ void ghash_wave_tables(LT& L, const SealKey& K, uint32_t wid, uint32_t lane) {
+    G4 basis[8];
+    basis[0] = ld4(K.H64);
+#pragma unroll
+    for (int j = 1; j < 8; j++) basis[j] = gmulx(basis[j - 1]);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const uint32_t b = lane + 64 * r;
+        G4 e = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            if (b & (0x80u >> j)) e = gxor(e, basis[j]);
+        st4(L.gt[wid][b], e);
+    }
+    for (uint32_t pr = lane; pr < 96; pr += 64) {
+        const uint32_t k = pr >> 4, nib = pr & 15;
+        G4 v = ld4(K.P[k]), e = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (nib & (0x8u >> j)) e = gxor(e, v);
+            v = gmulx(v);
+        }
+        st4(L.g4[wid][k][nib], e);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// fold the 64 lane partials: T = sum_l X_l * H^(63 - l), in lane 0
+template <typename LT>
+__device__ __forceinline__ G4 ghash_wave_fold(const LT& L, G4 X, uint32_t wid, uint32_t lane) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const G4 y = shfl_down4(X, 1 << k);
+        const G4 t = gmul_t4(L, X, L.g4[wid][k]);
+        if ((lane & ((2u << k) - 1)) == 0) X = gxor(t, y);
+    }
+    return X;
 }
 
 template <bool DEC, bool FRAMED>
@@ -473,35 +522,7 @@ __global__ __launch_bounds__(SEAL_THREADS) void k_seal_ctr(const uint8_t* __rest
         const uint64_t first = m - (np - 1) * PIECE_BLOCKS;
         const uint64_t b0 = pi == 0 ? 0 : first + (pi - 1) * PIECE_BLOCKS;
         const uint32_t q = (uint32_t)(pi == 0 ? first : PIECE_BLOCKS);
-        // this wave's tables: 8-bit Shoup table of H^64 (4 entries per lane), 4-bit tables of H^(2^k)
-        {
-            G4 basis[8];
-            basis[0] = ld4(K.H64);
-#pragma unroll
-            for (int j = 1; j < 8; j++) basis[j] = gmulx(basis[j - 1]);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const uint32_t b = lane + 64 * r;
-                G4 e = {0, 0, 0, 0};
-#pragma unroll
-                for (int j = 0; j < 8; j++)
-                    if (b & (0x80u >> j)) e = gxor(e, basis[j]);
-                st4(L.gt[wid][b], e);
-            }
-            for (uint32_t pr = lane; pr < 96; pr += 64) {
-                const uint32_t k = pr >> 4, nib = pr & 15;
-                G4 v = ld4(K.P[k]), e = {0, 0, 0, 0};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    if (nib & (0x8u >> j)) e = gxor(e, v);
-                    v = gmulx(v);
-                }
-                st4(L.g4[wid][k][nib], e);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        ghash_wave_tables(L, K, wid, lane);
 
         uint32_t rk[60];
 #pragma unroll
@@ -526,17 +547,108 @@ __global__ __launch_bounds__(SEAL_THREADS) void k_seal_ctr(const uint8_t* __rest
                 X = gxor(X, crypt_block<DEC, FRAMED>(s, d, len, gb, ksb, it.raw_len, it.wd));
             }
         }
-        // fold the 64 lane partials: T = sum_l X_l * H^(63 - l)
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            const G4 y = shfl_down4(X, 1 << k);
-            const G4 t = gmul_t4(L, X, L.g4[wid][k]);
-            if ((lane & ((2u << k) - 1)) == 0) X = gxor(t, y);
-        }
+        X = ghash_wave_fold(L, X, wid, lane);
         if (lane == 0) st4(parts + 4 * p, X);
         __builtin_amdgcn_wave_barrier();  // the tables are rebuilt for the next piece
     }
 }
+
+// ------------------------------------------------------------------ k_seal_auth
+// The GHASH half of k_seal_ctr<true, false> alone: the same pieces, the same 64-lane Horner scheme
+// and the same partials, so k_seal_prep and k_seal_tag<true> serve it unchanged -- but no AES, so no
+// Te replicas in LDS, no round keys in registers, no keystream and no store but the piece's partial.
+// The LDS holds the GHASH tables only (5.5 KiB per wave); WAVES per workgroup is the occupancy
+// choice (launch_seal).
+template <int WAVES>
+struct AuthLds {
+    uint32_t gt[WAVES][256][4];    // [wave][byte] Shoup 8-bit table of H^64
+    uint32_t g4[WAVES][6][16][4];  // [wave][level][nibble] Shoup 4-bit tables of H^(2^k)
+    uint32_t r8[256], r4[16];      // reduction of 8 / 4 shifted-out bits (xor into w0)
+};
+
+// block g of the item's ciphertext as GHASH takes it: zero-padded past the item's end, as
+// crypt_block<true, ...> pads it; a full block is one 16-byte load at whatever byte s + 16 g is
+__device__ __forceinline__ G4 auth_block(const uint8_t* s, uint64_t len, uint64_t g) {
+    const uint64_t at = 16 * g;
+    if (at + 16 <= len) {
+        const uint4 v = *(const uint4*)(s + at);
+        return {__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w)};
+    }
+    const uint32_t nb = (uint32_t)(len - at);
+    uint32_t in[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++)
+            if ((uint32_t)(4 * w + b) < nb) x |= (uint32_t)s[at + 4 * w + b] << (24 - 8 * b);
+        in[w] = x;
+    }
+    return {in[0], in[1], in[2], in[3]};
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_seal_auth(const uint8_t* __restrict__ src,
+                                                          const SealItem* __restrict__ items, uint64_t n_items,
+                                                          const SealKey* __restrict__ keys, uint64_t n_pieces,
+                                                          uint32_t* __restrict__ parts) {
+    __shared__ __attribute__((aligned(16))) AuthLds<WAVES> L;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid < 256) {
+        G4 v = {0, 0, 0, tid};
+        for (int k = 0; k < 8; k++) {
+            v = gmulx(v);
+            if (k == 3 && tid < 16) L.r4[tid] = v.w0;
+        }
+        L.r8[tid] = v.w0;
+    }
+    __syncthreads();
+
+    for (uint64_t p = (uint64_t)blockIdx.x * WAVES + wid; p < n_pieces; p += (uint64_t)gridDim.x * WAVES) {
+        // item owning piece p (items[].piece0 ascending), and the piece's blocks, as in k_seal_ctr
+        uint64_t lo = 0, hi = n_items;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (items[mid].piece0 <= p) lo = mid + 1;
+            else hi = mid;
+        }
+        const uint64_t ii = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(lo - 1));
+        const SealItem& it = items[ii];
+        const SealKey& K = keys[ii];
+        const uint64_t len = it.len, m = (len + 15) / 16;
+        const uint64_t pi = p - it.piece0, np = (m + PIECE_BLOCKS - 1) / PIECE_BLOCKS;
+        const uint64_t first = m - (np - 1) * PIECE_BLOCKS;
+        const uint64_t b0 = pi == 0 ? 0 : first + (pi - 1) * PIECE_BLOCKS;
+        const uint32_t q = (uint32_t)(pi == 0 ? first : PIECE_BLOCKS);
+        ghash_wave_tables(L, K, wid, lane);
+
+        const uint8_t* s = src + it.src_off;
+        const uint32_t S = (q + 63) / 64, pad = 64 * S - q;
+        G4 X = {0, 0, 0, 0};
+        // lane l takes blocks l - pad + 64 j: four loads in flight per lane, GHASH in order
+        for (uint32_t j = 0; j < S; j += 4) {
+            G4 c[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int32_t r = (int32_t)(lane + 64 * (j + u)) - (int32_t)pad;  // < 0 only for j + u == 0
+                c[u] = {0, 0, 0, 0};
+                if (j + u < S && r >= 0) c[u] = auth_block(s, len, b0 + (uint32_t)r);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (j + u < S) {  // wave-uniform
+                    if (j + u) X = gmul_h64(L, X, wid);
+                    X = gxor(X, c[u]);
+                }
+        }
+        X = ghash_wave_fold(L, X, wid, lane);
+        if (lane == 0) st4(parts + 4 * p, X);
+        __builtin_amdgcn_wave_barrier();  // the tables are rebuilt for the next piece
+    }
+}
+
+static_assert(SEAL_AUTH_WAVES >= 4 && 16384 % SEAL_AUTH_WAVES == 0, "r8 is filled by the first 256 lanes");
 
 // ------------------------------------------------------------------ k_seal_tag
 template <bool DEC>
@@ -621,8 +733,38 @@ uint32_t zstd_window_descriptor(uint64_t raw_len) {
 
 void launch_seal(hipStream_t st, bool dec, bool framed, const uint8_t* src, uint8_t* dst, const SealItem* it,
                  uint64_t n, const SealPads& pads, SealKey* k, uint64_t n_pieces, uint32_t* parts, uint8_t* ok) {
+    launch_seal(st, dec, framed, src, dst, it, n, pads, k, n_pieces, parts, ok, false);
+}
+
+void launch_seal(hipStream_t st, bool dec, bool framed, const uint8_t* src, uint8_t* dst, const SealItem* it,
+                 uint64_t n, const SealPads& pads, SealKey* k, uint64_t n_pieces, uint32_t* parts, uint8_t* ok,
+                 bool auth) {
     if (!n) return;
     hipLaunchKernelGGL(k_seal_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, it, n, pads, k);
+    if (auth) {
+        // the third mode: tags recomputed from the ciphertext alone.  SEAL_AUTH_WAVES = 8 waves per
+        // workgroup (44.6 KiB of LDS; at 109 VGPRs two of them are resident per CU, the 16 waves one
+        // 16-wave workgroup gives).  BW_SEAL_AUTH_WAVES=16 selects the one-workgroup-per-CU shape of
+        // k_seal_ctr for A/B runs (tools/check_bench.py; measured slower).  Either
+        // way a grid pass covers the 16,384 pieces a pass of k_seal_ctr covers.
+        static const bool wide = [] {
+            const char* e = getenv("BW_SEAL_AUTH_WAVES");
+            return e && atoi(e) == 16;
+        }();
+        if (n_pieces) {
+            const uint64_t waves = wide ? 16 : SEAL_AUTH_WAVES;
+            uint64_t grid = (n_pieces + waves - 1) / waves;
+            if (grid > 16384 / waves) grid = 16384 / waves;
+            if (wide)
+                hipLaunchKernelGGL(k_seal_auth<16>, dim3((unsigned)grid), dim3(64 * 16), 0, st, src, it, n, k, n_pieces, parts);
+            else
+                hipLaunchKernelGGL(k_seal_auth<SEAL_AUTH_WAVES>, dim3((unsigned)grid), dim3(64 * SEAL_AUTH_WAVES), 0, st, src,
+                                   it, n, k, n_pieces, parts);
+        }
+        hipLaunchKernelGGL(k_seal_tag<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, nullptr, it, n, k,
+                           parts, ok);
+        return;
+    }
     if (n_pieces) {
         uint64_t grid = (n_pieces + SEAL_THREADS / 64 - 1) / (SEAL_THREADS / 64);
         if (grid > 1024) grid = 1024;

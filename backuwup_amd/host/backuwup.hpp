@@ -643,6 +643,61 @@ private:
     const std::vector<bw_unpack_entry>& entries_;
 };
 
+// ------------------------------------------------------------------ check (no counterpart in the reference)
+// Over an open Restore: structure() = headers against index items and the layout of every blob
+// section, data() = every selected entry's bytes (BW_CHECK_AUTH: tags only, BW_CHECK_FULL: the unpack
+// chain with verify); auth() = AES-GCM tags of sealed items in a host buffer, nothing decrypted.
+class Check {
+public:
+    struct Structure {
+        std::vector<uint8_t> entry_flags;           // BW_CHECK_E_* per header entry
+        std::vector<uint8_t> item_status;           // per index item
+        std::vector<bw_check_packfile_stat> stats;  // per packfile
+        bw_check_counts counts{};
+    };
+
+    Check(Context& ctx, Restore& session, const PackfileTable& t, const std::vector<bw_unpack_entry>& entries, size_t n_items)
+        : ctx_(ctx), s_(session), n_pf_(t.tab.size()), n_entries_(entries.size()), n_items_(n_items) {}
+
+    Structure structure() {
+        Structure r;
+        r.entry_flags.resize(n_entries_ + 1);
+        r.item_status.resize(n_items_ + 1);
+        r.stats.resize(n_pf_ + 1);
+        check(bw_check_structure(s_.get(), r.entry_flags.data(), r.item_status.data(), r.stats.data(), &r.counts), ctx_.get());
+        r.entry_flags.resize(n_entries_);
+        r.item_status.resize(n_items_);
+        r.stats.resize(n_pf_);
+        return r;
+    }
+
+    // one status per header entry; select: one byte per entry, empty = all
+    std::vector<uint8_t> data(uint32_t mode, const std::vector<uint8_t>& select = {}) {
+        if (!select.empty() && select.size() != n_entries_) throw Error(BW_EINVAL, "check: one select byte per entry");
+        std::vector<uint8_t> st(n_entries_ + 1);
+        check(bw_check_data(s_.get(), mode, select.empty() ? nullptr : select.data(), st.data()), ctx_.get());
+        st.resize(n_entries_);
+        return st;
+    }
+
+    // ok per item: src_len includes the tag, infos holds info_len bytes per item, nonces 12
+    static std::vector<uint8_t> auth(Context& ctx, const std::array<uint8_t, 32>& prk, const std::vector<uint8_t>& src,
+                                     const std::vector<uint64_t>& src_off, const std::vector<uint64_t>& src_len,
+                                     const std::vector<uint8_t>& infos, uint32_t info_len, const std::vector<uint8_t>& nonces) {
+        std::vector<uint8_t> ok(src_off.size() + 1);
+        check(bw_auth(ctx.get(), prk.data(), src.data(), src_off.data(), src_len.data(), src_off.size(), infos.data(), info_len,
+                      nonces.data(), ok.data()),
+              ctx.get());
+        ok.resize(src_off.size());
+        return ok;
+    }
+
+private:
+    Context& ctx_;
+    Restore& s_;
+    size_t n_pf_, n_entries_, n_items_;
+};
+
 // ------------------------------------------------------------------ index files (blob_index.rs)
 using IndexEntry = std::pair<BlobHash, PackfileId>;
 

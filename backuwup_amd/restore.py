@@ -65,6 +65,7 @@ class Session:
                                                _ptr(items), items.shape[0], slots, ctypes.byref(h)), ctx.h)
         self.h = h
         self.n_entries, self.n_packfiles = int(en.size), int(pl.size if plan is not None else len(blobs))
+        self.n_items = int(items.shape[0])
 
     def close(self):
         if getattr(self, "h", None):

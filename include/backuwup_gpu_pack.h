@@ -440,6 +440,81 @@ int bw_prune_repack_device(bw_restore* session, const uint64_t* order, uint64_t 
 int bw_prune_repack(bw_restore* session, const uint64_t* order, uint64_t n_moved, const bw_packfile* plan,
                     uint64_t n_new, const uint8_t* new_ids, uint8_t* out);
 
+/* ---- check: is this store sound, are these bytes still the bytes that were sealed ----
+ * The reference never verifies what it has written; this goes past it as prune does.  Three layers,
+ * all synchronous: bw_auth(_device) recomputes AES-GCM tags without decrypting, bw_check_structure
+ * cross-checks headers and index items without reading a blob byte, bw_check_data reads every
+ * selected entry's bytes.  The last two work over an open restore session and change nothing in it. */
+
+/* bw_open_device's verdicts without its plaintext: the same tables minus d_dst and dst_off.
+ * src_len[i] includes the tag (>= 16, else BW_EINVAL); ok[i] (host) = 1 exactly where bw_open_device
+ * sets ok[i] = 1, for every input.  The tag is recomputed from the ciphertext alone (GHASH, plus two
+ * AES blocks per item for H and E(J0)); the key comes from prk, so only its owner can make a tag
+ * verify.  The source ranges are read once and no byte of device memory outside the context's own
+ * scratch is written. */
+int bw_auth_device(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
+                   const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                   const uint8_t* nonces, uint8_t* ok);
+/* Same over a host buffer: the source is uploaded and nothing but ok comes back. */
+int bw_auth(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
+            const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+            const uint8_t* nonces, uint8_t* ok);
+
+/* Per-entry bits of bw_check_structure. */
+#define BW_CHECK_E_RANGE 1u     /* 12 + length leaves the packfile's blob section, or length < 16: BW_UNPACK_ERANGE's rule */
+#define BW_CHECK_E_ORDER 2u     /* offset != the sum of 12 + length over the earlier entries of the packfile */
+#define BW_CHECK_E_UNINDEXED 4u /* no index item is (this hash, this packfile's id): restore never finds it   */
+#define BW_CHECK_E_SHADOWED 8u  /* an earlier entry of the packfile has the hash: the header scan stops there */
+/* Statuses beside BW_UNPACK_* and BW_RESTORE_* (which they never collide with). */
+enum {
+    BW_CHECK_SKIPPED = 32,   /* bw_check_data: the entry was not selected                               */
+    BW_CHECK_IDUPLICATE = 33 /* bw_check_structure: the item equals, in both fields, an item before it  */
+};
+typedef struct bw_check_packfile_stat {
+    uint64_t n_entries;
+    uint64_t n_range, n_order, n_unindexed, n_shadowed; /* entries with the flag                       */
+    uint64_t claimed_bytes; /* the sum of 12 + length over the packfile's entries                       */
+    uint64_t section_bytes; /* size - 8 - header_len (0 when the header alone exceeds the size)         */
+    int64_t tail;           /* section_bytes - claimed_bytes: < 0 truncated, > 0 trailing bytes         */
+} bw_check_packfile_stat;
+typedef struct bw_check_counts {
+    uint64_t n_entries, n_range, n_order, n_unindexed, n_shadowed, claimed_bytes, section_bytes; /* sums */
+    uint64_t n_items_ok, n_items_nopackfile, n_items_mismatch, n_items_duplicate;
+    uint64_t n_packfiles_clean; /* packfiles without a flagged entry and with tail == 0                 */
+} bw_check_counts;
+
+/* Everything that needs no blob byte, from the session's device copies of the entries, the index
+ * items, the ids and its two locator tables.  The session's entries must come in packfile order, as
+ * bw_unpack_headers returns them (else BW_EINVAL).  All outputs are host arrays.
+ *   entry_flags[e] (one byte per session entry): BW_CHECK_E_* bits.  A shadowed entry is not also
+ *     reported unindexed.  The expected offsets come from one segmented exclusive sum over all entries
+ *     (segments = packfiles), so a packfile of 100,000 entries and 1,000 packfiles of one entry cost the same.
+ *   item_status[i] (one byte per index item): BW_RESTORE_OK; BW_RESTORE_ENOPACKFILE, the id is not
+ *     among the session's ids; BW_RESTORE_EMISMATCH, that packfile's header lacks the hash;
+ *     BW_CHECK_IDUPLICATE, an item with a lower index has the same hash and id (the lowest of such a
+ *     group is OK; which one wins does not depend on scheduling).  An item that does not resolve
+ *     keeps its own status however often it is repeated.
+ *   stats[p]: one record per packfile; *counts: their sums, the four item statuses, the clean packfiles.
+ * A session without entries, items or packfiles is fine: BW_OK and zeros. */
+int bw_check_structure(bw_restore* session, uint8_t* entry_flags, uint8_t* item_status, bw_check_packfile_stat* stats,
+                       bw_check_counts* counts);
+
+/* Every selected entry's bytes.  select: one byte per session entry, NULL = all; status[e] (host,
+ * one byte per session entry): BW_CHECK_SKIPPED for an entry not selected, BW_UNPACK_ERANGE for one
+ * with BW_CHECK_E_RANGE (it is never read), else by mode:
+ *   BW_CHECK_AUTH: the blob is authenticated where it lies in the session's packfiles (bw_auth_device's
+ *     path: nonce at 8 + header_len + offset, key info = the entry's hash): BW_UNPACK_OK or _ETAG.  No
+ *     decode slot is used and nothing is decrypted; the selection goes in one launch sequence.
+ *   BW_CHECK_FULL: the unpack chain with BW_UNPACK_VERIFY, `slots` entries at a time as
+ *     bw_restore_files_device drives it: BW_UNPACK_OK, _ETAG, _EZSTD or _EDIGEST; an entry of kind
+ *     Tree that passes is parsed in its slot, and BW_RESTORE_EFORMAT is what the parser refuses.  No
+ *     regenerated byte leaves the device.
+ * For every selected entry, the AUTH status is BW_UNPACK_OK exactly when the FULL status is neither
+ * BW_UNPACK_ETAG nor BW_UNPACK_ERANGE. */
+#define BW_CHECK_AUTH 1u
+#define BW_CHECK_FULL 2u
+int bw_check_data(bw_restore* session, uint32_t mode, const uint8_t* select, uint8_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,45 @@ pub mod ffi {
         pub pad: u32,
     }
 
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_check_packfile_stat {
+        pub n_entries: u64,
+        pub n_range: u64,
+        pub n_order: u64,
+        pub n_unindexed: u64,
+        pub n_shadowed: u64,
+        pub claimed_bytes: u64,
+        pub section_bytes: u64,
+        pub tail: i64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_check_counts {
+        pub n_entries: u64,
+        pub n_range: u64,
+        pub n_order: u64,
+        pub n_unindexed: u64,
+        pub n_shadowed: u64,
+        pub claimed_bytes: u64,
+        pub section_bytes: u64,
+        pub n_items_ok: u64,
+        pub n_items_nopackfile: u64,
+        pub n_items_mismatch: u64,
+        pub n_items_duplicate: u64,
+        pub n_packfiles_clean: u64,
+    }
+
+    pub const BW_CHECK_E_RANGE: u8 = 1;
+    pub const BW_CHECK_E_ORDER: u8 = 2;
+    pub const BW_CHECK_E_UNINDEXED: u8 = 4;
+    pub const BW_CHECK_E_SHADOWED: u8 = 8;
+    pub const BW_CHECK_SKIPPED: u8 = 32;
+    pub const BW_CHECK_IDUPLICATE: u8 = 33;
+    pub const BW_CHECK_AUTH: u32 = 1;
+    pub const BW_CHECK_FULL: u32 = 2;
+
     pub const BW_RESTORE_OK: u8 = 0;
     pub const BW_RESTORE_ENOTFOUND: u8 = 16;
     pub const BW_RESTORE_EMISMATCH: u8 = 17;
@@ -451,6 +490,15 @@ pub mod ffi {
                                       plan: *const bw_packfile, n_new: u64, new_ids: *const u8, d_out: *mut u8) -> c_int;
         pub fn bw_prune_repack(session: *mut bw_restore, order: *const u64, n_moved: u64, plan: *const bw_packfile,
                                n_new: u64, new_ids: *const u8, out: *mut u8) -> c_int;
+
+        pub fn bw_auth_device(ctx: *mut bw_ctx, prk: *const u8, d_src: *const u8, src_off: *const u64,
+                              src_len: *const u64, n: u64, info: *const u8, info_len: u32, nonces: *const u8,
+                              ok: *mut u8) -> c_int;
+        pub fn bw_auth(ctx: *mut bw_ctx, prk: *const u8, src: *const u8, src_off: *const u64, src_len: *const u64,
+                       n: u64, info: *const u8, info_len: u32, nonces: *const u8, ok: *mut u8) -> c_int;
+        pub fn bw_check_structure(session: *mut bw_restore, entry_flags: *mut u8, item_status: *mut u8,
+                                  stats: *mut bw_check_packfile_stat, counts: *mut bw_check_counts) -> c_int;
+        pub fn bw_check_data(session: *mut bw_restore, mode: u32, select: *const u8, status: *mut u8) -> c_int;
 
         pub fn bw_profile_enable(ctx: *mut bw_ctx, on: c_int) -> c_int;
         pub fn bw_profile_read(ctx: *mut bw_ctx, stage_ms: *mut f64, n_batches: *mut u64) -> c_int;
