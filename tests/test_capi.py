@@ -26,7 +26,9 @@ def test_header_declares_the_boundary():
     names = declared_functions()
     for required in ["bw_fastcdc_chunks", "bw_blake3_hash", "bw_blake3_hash_many", "bw_index_seed",
                      "bw_index_check_insert", "bw_process_files", "bw_process_files_device", "bw_results",
-                     "bw_partition_by_owner", "bw_index_check_insert_device", "bw_scatter_verdicts"]:
+                     "bw_partition_by_owner", "bw_index_check_insert_device", "bw_scatter_verdicts",
+                     "bw_partition_buckets", "bw_index_check_insert_buckets", "bw_scatter_buckets",
+                     "bw_exchange_dedup", "bw_comm_init_local"]:
         assert required in names
 
 
