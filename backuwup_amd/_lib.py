@@ -19,7 +19,11 @@ BW_OPT_DEPTH, BW_OPT_SCAN_SMALL_BYTES, BW_OPT_CAND_CAP, BW_OPT_STAGE_CHUNK, BW_O
 BW_OPT_SCAN_WAVES, BW_OPT_LATENCY_STREAM, BW_OPT_ZSTD_SLOTS, BW_OPT_ZSTD_BATCH_BYTES = 6, 7, 8, 9
 BW_OPT_ORDER_HASH, BW_OPT_SPLIT = 10, 11
 BW_OPT_PROFILE_MASK, BW_OPT_SCAN_FIRST, BW_OPT_B3_UPPER, BW_OPT_B3_GROUP = 12, 13, 14, 15
-BW_B3_LOADS_DEFAULT = 2  # the library's BW_OPT_B3_LOADS default (bw_capi.hip)
+# bw_batch_counters: index -> name, in the order of the header's BW_BC_* enum
+BW_BC_NAMES = ("scan_tiles", "ovf_tiles", "cand_found", "cand_stored", "trunc", "cdc_files", "segments",
+               "serial_files", "tile_bytes", "seg_bytes")
+BW_BC_NONE = (1 << 64) - 1  # "trunc" when every candidate fit
+BW_B3_LOADS_DEFAULT = 2 # the library's BW_OPT_B3_LOADS default (bw_capi.hip)
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -184,6 +188,8 @@ SIGNATURES = [
     ("bw_scatter_verdicts", ctypes.c_int, [vp, vp, vp, ctypes.c_uint64, vp]),
     ("bw_batch_views", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.POINTER(vp), ctypes.POINTER(vp),
                                       ctypes.POINTER(vp), u64p]),
+    ("bw_batch_counters", ctypes.c_int, [vp, ctypes.c_uint64, u64p, ctypes.c_uint32,
+                                         ctypes.POINTER(ctypes.c_uint32)]),
     ("bw_partition_buckets", ctypes.c_int, [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, vp, vp,
                                             vp]),
     ("bw_index_check_insert_buckets", ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp]),

@@ -783,6 +783,16 @@ class Context:
                                      ctypes.byref(mx)), self.h)
         return n.value, d.value, dup.value, mx.value
 
+    def batch_counters(self, ticket=0):
+        """bw_batch_counters of a batch already waited on (0 = the most recent) -> dict keyed by
+        _lib.BW_BC_NAMES: which way the batch took through the chunker.  Touches no device."""
+        k = len(_lib.BW_BC_NAMES)
+        out = (ctypes.c_uint64 * k)()
+        n = ctypes.c_uint32()
+        check(self._L.bw_batch_counters(self.h, int(ticket), out, k, ctypes.byref(n)), self.h)
+        assert n.value == k, "BW_BC_NAMES is out of step with the header's BW_BC_COUNT"
+        return {name: int(out[i]) for i, name in enumerate(_lib.BW_BC_NAMES)}
+
     def exchange_dedup(self, comm, ticket=0):
         """Batch `ticket` (submitted with BW_F_NO_DEDUP) through the digest-prefix exchange of
         `comm` (a backuwup_amd.comm.Comm): its verdicts land in the batch's results."""

@@ -1125,6 +1125,11 @@ static int submit(bw_ctx* c, Slot& s, const uint8_t* d_data, uint64_t data_len, 
     if (c->prof) c->ev_pending[c->ev_set] = true;
     HIPCHK(c, hipGetLastError());
     s.max_blobs = max_blobs;
+    s.geo_tiles = n_tiles;
+    s.geo_cfiles = ncf;
+    s.geo_segs = nseg;
+    s.geo_tile_bytes = tile_bytes;
+    s.geo_seg_bytes = L;
     s.dedup = do_dedup;
     s.hashed = do_hash;
     s.comm = nullptr;
@@ -1570,6 +1575,41 @@ extern "C" int bw_batch_views(bw_ctx* c, uint64_t ticket, const uint64_t** d_n_b
     if (d_digests) *d_digests = P<uint8_t>(s->digests);
     if (d_is_dup) *d_is_dup = P<uint8_t>(s->is_dup);
     if (max_blobs) *max_blobs = s->max_blobs;
+    return BW_OK;
+}
+
+// Which way batch `ticket` took through the chunker: the counters its wait already brought back
+// (slot_results reads the same pinned copy) and the geometry submit laid out.  Nothing is
+// launched, copied or waited for.
+extern "C" int bw_batch_counters(bw_ctx* c, uint64_t ticket, uint64_t* out, uint32_t cap, uint32_t* n) {
+    if (!c || !n || (cap && !out)) return BW_EINVAL;
+    Slot* s = slot_of(c, ticket ? ticket : c->last_ticket);
+    if (!s) {
+        c->err = "ticket " + std::to_string(ticket) + " is not (or no longer) held by the context";
+        return BW_ESTATE;
+    }
+    if (s->tail_ticket) {
+        c->err = "the batch was split in two parts (BW_OPT_SPLIT): no single set of counters";
+        return BW_ESTATE;
+    }
+    hipSetDevice(c->device);
+    if (!s->res.p || hipEventQuery(s->done) != hipSuccess) {
+        c->err = "the batch's results have not arrived: bw_wait(ticket) first";
+        return BW_ESTATE;
+    }
+    *n = BW_BC_COUNT;
+    if (cap < BW_BC_COUNT) return BW_ENOSPC;
+    const uint64_t* ctr = (const uint64_t*)s->res.p;
+    out[BW_BC_SCAN_TILES] = s->geo_tiles;
+    out[BW_BC_OVF_TILES] = ctr[C_NOVF];
+    out[BW_BC_CAND_FOUND] = ctr[C_CANDTOTAL];
+    out[BW_BC_CAND_STORED] = ctr[C_NCAND];
+    out[BW_BC_TRUNC] = s->geo_tiles ? ctr[C_TRUNC] : ~0ull;  // without CDC files nothing writes it
+    out[BW_BC_CDC_FILES] = s->geo_cfiles;
+    out[BW_BC_SEGMENTS] = s->geo_segs;
+    out[BW_BC_SERIAL_FILES] = ctr[C_NINVALID];
+    out[BW_BC_TILE_BYTES] = s->geo_tile_bytes;
+    out[BW_BC_SEG_BYTES] = s->geo_seg_bytes;
     return BW_OK;
 }
 

@@ -682,11 +682,18 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_chains(Walker W, const
     const SegDesc sd = segs[j];
     uint64_t s = sd.start, cptr = tile_off[s >> W.mk.tile_shift];
     uint32_t n = 0;
+    // The chain runs one cut beyond its first cut at or past the segment's end.  A segment without
+    // any candidate is crossed by a forced cut (max after the previous one), and a chain that
+    // stopped at its own forced cut shared no cut with the true chain, which then passed its last
+    // entry unmerged and sent the whole file to the serial walker; the next content-defined cut is
+    // where the two meet.
+    bool past = false;
     for (;;) {
         const uint64_t c = walk_next(W, s, sd.file_end, cptr);
         if (n < (uint32_t)CHAIN_CAP && bw_lane() == 0) chains[j * CHAIN_CAP + n] = c;
         n++;
-        if (c >= sd.end || n > (uint32_t)CHAIN_CAP) break;
+        if (n > (uint32_t)CHAIN_CAP || c >= sd.file_end || (c >= sd.end && past)) break;
+        past = c >= sd.end;
         s = c;
     }
     if (bw_lane() == 0) { chain_n[j] = n; chain_cptr[j] = cptr; }

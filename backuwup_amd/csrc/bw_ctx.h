@@ -43,6 +43,9 @@ struct Slot {
     bool meta_on_done = false;  // the staging's last upload is covered by `done` (no event of its own)
     uint64_t ticket = 0;  // 0: empty
     uint64_t max_blobs = 0;
+    // the batch's geometry as submit laid it out (bw_batch_counters): scan tiles, CDC files,
+    // segments, bytes per tile and per segment
+    uint64_t geo_tiles = 0, geo_cfiles = 0, geo_segs = 0, geo_tile_bytes = 0, geo_seg_bytes = 0;
     bool dedup = false;
     bool hashed = false;          // digests computed (not BW_F_NO_HASH): the exchange may gate them
     bw_comm* comm = nullptr;      // the batch went through this communicator's exchange: waits on it

@@ -325,6 +325,30 @@ int bw_scatter_verdicts(bw_ctx* ctx, const uint8_t* d_verdict, const uint64_t* d
  * exchanged batch are final once bw_wait(ticket) returned. */
 int bw_batch_views(bw_ctx* ctx, uint64_t ticket, const uint64_t** d_n_blobs, const uint8_t** d_digests,
                    uint8_t** d_is_dup, uint64_t* max_blobs);
+/* Which way batch `ticket` (0 = the most recent) took through the chunker: out[BW_BC_*], values the
+ * host already holds once bw_wait(ticket) returned -- the counters that came back with the results
+ * and the geometry bw_submit_* laid out.  Read-only: no kernel, no copy, no synchronization.
+ * *n = BW_BC_COUNT; cap < BW_BC_COUNT gives BW_ENOSPC.  BW_ESTATE, like bw_batch_views, for a ticket
+ * the ring no longer holds and for a batch split by BW_OPT_SPLIT (its two parts have counters of
+ * their own), and also for a batch whose results have not arrived yet (bw_wait first).  The
+ * synchronous helpers (bw_process_files, bw_fastcdc_chunks) run outside the ring and have no ticket. */
+enum {
+    BW_BC_SCAN_TILES = 0,   /* gear-scan tiles of the batch (0: no file went to CDC)               */
+    BW_BC_OVF_TILES = 1,    /* tiles with more than 16 candidates or flagged blocks: their exact
+                               candidate list came from the rescan, not from the scan's fast path  */
+    BW_BC_CAND_FOUND = 2,   /* gear candidates found                                               */
+    BW_BC_CAND_STORED = 3,  /* of those, stored in the candidate array (less: see BW_BC_TRUNC)     */
+    BW_BC_TRUNC = 4,        /* first byte position whose candidates the array could not hold; the
+                               walkers test the bytes from there on themselves.  ~0: all fit       */
+    BW_BC_CDC_FILES = 5,    /* files above small_file_threshold                                    */
+    BW_BC_SEGMENTS = 6,     /* segments those files were cut into for the speculative chains       */
+    BW_BC_SERIAL_FILES = 7, /* CDC files whose chains did not merge (or BW_F_SERIAL_RESOLVE): walked
+                               serially from their first byte                                      */
+    BW_BC_TILE_BYTES = 8,   /* bytes per scan tile (BW_OPT_SCAN_SMALL_BYTES)                       */
+    BW_BC_SEG_BYTES = 9,    /* bytes per segment                                                   */
+    BW_BC_COUNT = 10
+};
+int bw_batch_counters(bw_ctx* ctx, uint64_t ticket, uint64_t* out, uint32_t cap, uint32_t* n);
 /* d_buckets[n_owners][cap][32] = digests by owner, canonical order inside each bucket;
  * d_perm[n_owners][cap] = source index; d_counts[n_owners] (device u64).  n = *d_n (device),
  * max_n its host bound. */

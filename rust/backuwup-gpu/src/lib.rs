@@ -354,6 +354,7 @@ pub mod ffi {
                                    d_is_dup: *mut u8) -> c_int;
         pub fn bw_batch_views(ctx: *mut bw_ctx, ticket: u64, d_n_blobs: *mut *const u64, d_digests: *mut *const u8,
                               d_is_dup: *mut *mut u8, max_blobs: *mut u64) -> c_int;
+        pub fn bw_batch_counters(ctx: *mut bw_ctx, ticket: u64, out: *mut u64, cap: u32, n: *mut u32) -> c_int;
         pub fn bw_partition_buckets(ctx: *mut bw_ctx, d_digests: *const u8, d_n: *const u64, max_n: u64, cap: u64,
                                     n_owners: u32, d_buckets: *mut u8, d_perm: *mut u64, d_counts: *mut u64) -> c_int;
         pub fn bw_index_check_insert_buckets(ctx: *mut bw_ctx, d_buckets: *const u8, d_counts: *const u64,
