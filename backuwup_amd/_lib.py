@@ -281,6 +281,11 @@ SIGNATURES = [
     ("bw_check_structure", ctypes.c_int, [vp, u8p, u8p, ctypes.POINTER(BwCheckPackfileStat),
                                           ctypes.POINTER(BwCheckCounts)]),
     ("bw_check_data", ctypes.c_int, [vp, ctypes.c_uint32, u8p, u8p]),
+    ("bw_reseal_device", ctypes.c_int, [vp, vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, vp, u64p,
+                                        u8p]),
+    ("bw_reseal", ctypes.c_int, [vp, vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, vp, u64p, u8p]),
+    ("bw_rekey_store_device", ctypes.c_int, [vp, vp, vp, u8p, u8p]),
+    ("bw_rekey_store", ctypes.c_int, [vp, vp, vp, u8p, u8p]),
     ("bw_profile_enable", ctypes.c_int, [vp, ctypes.c_int]),
     ("bw_fastcdc_chunks_hashed", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint32, vp, ctypes.c_uint64, u64p, u64p]),

@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libbackuwup_amd.so")
 LIB_DEBUG = os.path.join(HERE, "libbackuwup_amd_debug.so")
 SOURCES = ["bw_capi.hip", "bw_cdc.hip", "bw_blake3.hip", "bw_dedup.hip", "bw_comm.hip", "bw_tree.hip", "bw_seal.hip",
            "bw_pack.hip", "bw_zstd.hip", "bw_dropin.hip", "bw_stream.hip", "bw_capi_pack.hip", "bw_b3_small.hip", "bw_zstd_dec.hip",
-           "bw_restore.hip", "bw_prune.hip", "bw_check.hip"]
+           "bw_restore.hip", "bw_prune.hip", "bw_check.hip", "bw_rekey.hip"]
 HEADERS = ["backuwup_gpu.h", "backuwup_gpu_pack.h"]  # include/
 ROCM_LIB = "/opt/rocm/lib"
 ARCH = os.environ.get("BW_OFFLOAD_ARCH", "gfx950")
@@ -30,7 +30,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # the restore session, bw_restore.hip, and prune and check over it, bw_prune.hip, bw_check.hip)
 OFF_PATH = ("bw_zstd.hip", "bw_seal.hip", "bw_pack.hip", "bw_tree.hip", "bw_comm.hip", "bw_dropin.hip", "bw_stream.hip",
             "bw_capi_pack.hip", "bw_b3_small.hip", "bw_b3_small.h", "bw_zstd_dec.hip", "bw_zstd_dec_core.h",
-            "bw_unpack.h", "bw_restore.hip", "bw_restore.h", "bw_prune.hip", "bw_prune.h", "bw_check.hip", "bw_check.h", "bw_seal.h")
+            "bw_unpack.h", "bw_restore.hip", "bw_restore.h", "bw_prune.hip", "bw_prune.h", "bw_check.hip", "bw_check.h", "bw_seal.h",
+            "bw_rekey.hip")
 
 
 def _code_only(text):

@@ -165,6 +165,129 @@ extern "C" int bw_open(bw_ctx* c, const uint8_t prk[32], const uint8_t* src, con
     return seal_host(c, true, prk, src, src_off, src_len, n, info, info_len, nonces, dst, dst_off, ok);
 }
 
+// ------------------------------------------------------------------ reseal
+// Items under old_prk become the same plaintexts under new_prk (and new nonces) without a plaintext
+// byte stored anywhere: kernels k_reseal_ctr and k_reseal_tag in bw_seal.hip.
+
+// true when an output range meets another output range or a source range (addresses a + off)
+static bool reseal_overlap(const uint8_t* src, const uint64_t* src_off, const uint8_t* dst, const uint64_t* dst_off,
+                           const uint64_t* len, uint64_t n) {
+    struct Iv {
+        uint64_t lo, hi;
+        bool out;
+    };
+    std::vector<Iv> v(2 * n);
+    for (uint64_t i = 0; i < n; i++) {
+        v[2 * i] = Iv{(uint64_t)(uintptr_t)src + src_off[i], (uint64_t)(uintptr_t)src + src_off[i] + len[i], false};
+        v[2 * i + 1] = Iv{(uint64_t)(uintptr_t)dst + dst_off[i], (uint64_t)(uintptr_t)dst + dst_off[i] + len[i], true};
+    }
+    std::sort(v.begin(), v.end(), [](const Iv& a, const Iv& b) { return a.lo < b.lo; });
+    uint64_t end_src = 0, end_out = 0;  // the furthest end of the ranges that start no later
+    for (const Iv& x : v) {
+        if (x.lo < end_out || (x.out && x.lo < end_src)) return true;
+        (x.out ? end_out : end_src) = std::max(x.out ? end_out : end_src, x.hi);
+    }
+    return false;
+}
+
+int bw_reseal_items(bw_ctx* c, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* d_src,
+                    const uint64_t* src_off, const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                    const uint32_t* info_lens, const uint8_t* nonces, const uint8_t* new_nonces, uint8_t* d_dst,
+                    const uint64_t* dst_off, uint8_t* ok) {
+    if (!c || !old_prk || !new_prk || info_len > BW_SEAL_MAX_INFO) return BW_EINVAL;
+    if (n && (!d_src || !src_off || !src_len || !nonces || (info_len && !info) || !d_dst || !dst_off || !ok)) return BW_EINVAL;
+    hipSetDevice(c->device);
+    if (!n) return BW_OK;
+    for (uint64_t i = 0; i < n; i++)
+        if (src_len[i] < 16 || (info_lens && info_lens[i] > info_len)) return BW_EINVAL;
+    if (reseal_overlap(d_src, src_off, d_dst, dst_off, src_len, n)) {
+        c->err = "reseal: an output range overlaps another output range or a source range";
+        return BW_EINVAL;
+    }
+    if (!c->seal_done) HIPCHK(c, hipEventCreateWithFlags(&c->seal_done, hipEventDisableTiming));
+    if (c->seal_pending) {
+        hipEventSynchronize(c->seal_done);
+        c->seal_pending = false;
+    }
+    // two item tables only where the nonces change: they differ in nothing else
+    const uint64_t sides = new_nonces ? 2 : 1;
+    const size_t bytes = n * sizeof(SealItem);
+    if (int rc = ensure_host(c, c->seal_stage, sides * bytes)) return rc;
+    SealItem* it = (SealItem*)c->seal_stage.p;
+    std::vector<uint64_t> piece0(n);
+    uint64_t pieces = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        piece0[i] = pieces;
+        pieces += seal_pieces(src_len[i] - 16);
+    }
+    parallel_ranges(n, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; i++) {
+            const uint32_t il = info_lens ? info_lens[i] : info_len;
+            seal_fill_item(&it[i], src_off[i], src_len[i] - 16, dst_off[i], piece0[i], nonces + 12 * i,
+                           info + (uint64_t)info_len * i, il);
+            if (new_nonces)
+                seal_fill_item(&it[n + i], src_off[i], src_len[i] - 16, dst_off[i], piece0[i], new_nonces + 12 * i,
+                               info + (uint64_t)info_len * i, il);
+        }
+    });
+    const size_t part_bytes = (pieces + 1) * 16;
+    if (int rc = ensure(c, c->seal_items, sides * bytes)) return rc;
+    if (int rc = ensure(c, c->seal_keys, 2 * n * sizeof(SealKey))) return rc;
+    if (int rc = ensure(c, c->seal_parts, 2 * part_bytes)) return rc;
+    if (int rc = ensure(c, c->seal_ok, n)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->seal_items.p, it, sides * bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->seal_done, c->stream));
+    c->seal_pending = true;
+    SealPads pads_o, pads_n;
+    seal_pads(old_prk, &pads_o);
+    seal_pads(new_prk, &pads_n);
+    const SealItem* d_it = P<SealItem>(c->seal_items);
+    launch_reseal(c->stream, d_src, d_dst, d_it, new_nonces ? d_it + n : d_it, n, pads_o, pads_n, P<SealKey>(c->seal_keys),
+                  P<SealKey>(c->seal_keys) + n, pieces, P<uint32_t>(c->seal_parts),
+                  P<uint32_t>(c->seal_parts) + part_bytes / 4, P<uint8_t>(c->seal_ok));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(ok, c->seal_ok.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BW_OK;
+}
+
+extern "C" int bw_reseal_device(bw_ctx* c, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* d_src,
+                                const uint64_t* src_off, const uint64_t* src_len, uint64_t n, const uint8_t* info,
+                                uint32_t info_len, const uint8_t* nonces, const uint8_t* new_nonces, uint8_t* d_dst,
+                                const uint64_t* dst_off, uint8_t* ok) {
+    return bw_reseal_items(c, old_prk, new_prk, d_src, src_off, src_len, n, info, info_len, nullptr, nonces, new_nonces, d_dst,
+                           dst_off, ok);
+}
+
+// the source is uploaded into one staging area ([src | dst]); only the output ranges come back
+extern "C" int bw_reseal(bw_ctx* c, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* src,
+                         const uint64_t* src_off, const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                         const uint8_t* nonces, const uint8_t* new_nonces, uint8_t* dst, const uint64_t* dst_off, uint8_t* ok) {
+    if (!c || (n && (!src || !src_off || !src_len || !dst || !dst_off))) return BW_EINVAL;
+    hipSetDevice(c->device);
+    uint64_t s_end = 0, d_end = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (src_len[i] < 16) return BW_EINVAL;
+        s_end = std::max(s_end, src_off[i] + src_len[i]);
+        d_end = std::max(d_end, dst_off[i] + src_len[i]);
+    }
+    if (n && reseal_overlap(src, src_off, dst, dst_off, src_len, n)) {
+        c->err = "reseal: an output range overlaps another output range or a source range";
+        return BW_EINVAL;
+    }
+    const uint64_t d_base = (s_end + 255) & ~255ull;
+    if (int rc = ensure(c, c->seal_io, d_base + d_end + 16)) return rc;
+    uint8_t* io = P<uint8_t>(c->seal_io);
+    if (s_end) HIPCHK(c, hipMemcpyAsync(io, src, s_end, hipMemcpyHostToDevice, c->stream));
+    if (int rc = bw_reseal_device(c, old_prk, new_prk, io, src_off, src_len, n, info, info_len, nonces, new_nonces, io + d_base,
+                                  dst_off, ok))
+        return rc;
+    for (uint64_t i = 0; i < n; i++)
+        HIPCHK(c, hipMemcpyAsync(dst + dst_off[i], io + d_base + dst_off[i], src_len[i], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BW_OK;
+}
+
 // ------------------------------------------------------------------ packfiles (§8f row 4)
 // Manager::write_packfiles / serialize_packfile (pack.rs:115-227); kernels in bw_pack.hip.
 

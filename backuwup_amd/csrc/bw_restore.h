@@ -246,4 +246,5 @@ struct bw_restore {
     DevBuf pf_buf;    // bw_restore_open_host: the packfiles
     DevBuf pr_bits, pr_front[2], pr_ctr, pr_err, pr_stat, pr_tab, pr_hdr;  // prune (bw_prune.hip)
     DevBuf ck_buf;  // check (bw_check.hip)
+    DevBuf rk_buf;  // rekey (bw_rekey.hip)
 };

@@ -336,7 +336,7 @@ extern "C" int bw_restore_close(bw_restore* s) {
     hipStreamSynchronize(s->c->stream);
     for (DevBuf* b : {&s->ids, &s->items, &s->d_entries, &s->id_tab, &s->item_tab, &s->item_pos, &s->entry_tab, &s->slot_buf,
                       &s->q, &s->tab, &s->run, &s->emit, &s->win, &s->pf_buf, &s->pr_bits, &s->pr_front[0],
-                      &s->pr_front[1], &s->pr_ctr, &s->pr_err, &s->pr_stat, &s->pr_tab, &s->pr_hdr, &s->ck_buf})
+                      &s->pr_front[1], &s->pr_ctr, &s->pr_err, &s->pr_stat, &s->pr_tab, &s->pr_hdr, &s->ck_buf, &s->rk_buf})
         free_dev(*b);
     delete s;
     return BW_OK;

@@ -24,6 +24,10 @@
 //   k_seal_tag   one lane per item: folds the piece partials with H^PIECE_BLOCKS (pieces are
 //                cut from the item's end, so only the first is ragged), appends the length block and masks with E(J0); sealing
 //                stores the tag after the ciphertext, opening compares it (ok flag).
+//   k_seal_auth  the GHASH half of k_seal_ctr alone: tags recomputed, nothing decrypted (check).
+//   k_reseal_ctr, k_reseal_tag
+//                k_seal_ctr and k_seal_tag with two keys: ciphertext under one key to ciphertext under
+//                another in one pass, both GHASH side by side, no plaintext stored (rekey).
 //
 // GF(2^128) elements are four big-endian words w0..w3 of the block (GCM bit order: the MSB of
 // w0 is the coefficient of x^0); multiplication by x is a right shift by one with 0xE1 << 120
@@ -262,15 +266,17 @@ struct SealLds {
 
 #define SEAL_SEL(k) (0x0c0c0000u | ((4u + (k)) << 8))          // (byte k of w) << 8 | lane_off
 
-template <int OFF>
-__device__ __forceinline__ uint32_t te_at(const SealLds& L, uint32_t addr) {
+template <int OFF, typename LT>
+__device__ __forceinline__ uint32_t te_at(const LT& L, uint32_t addr) {
     return *(const uint32_t*)((const uint8_t*)&L.te[0][0] + addr + OFF);
 }
 
 // Two AES-256 encryptions of counter blocks (n0, n1, n2, ctr), words big-endian, interleaved so
 // one block's LDS lookups overlap the other's xors.  Round 1 starts from r1 (its nonce-word
-// terms, precomputed per item): only the counter word's four lookups remain.
-__device__ __forceinline__ void aes_ctr2(const SealLds& L, const uint32_t* rk, const uint32_t* r1, uint32_t lane_off,
+// terms, precomputed per item): only the counter word's four lookups remain.  LT: SealLds or
+// ResealLds (the same te); rk: 60 words, in registers (k_seal_ctr) or in LDS (k_reseal_ctr).
+template <typename LT>
+__device__ __forceinline__ void aes_ctr2(const LT& L, const uint32_t* rk, const uint32_t* r1, uint32_t lane_off,
                                          uint32_t ca, uint32_t cb, uint32_t oa[4], uint32_t ob[4]) {
 #define A0(w, k) te_at<0>(L, __builtin_amdgcn_perm((w), lane_off, SEAL_SEL(k)))
 #define A1(w, k) te_at<128>(L, __builtin_amdgcn_perm((w), lane_off, SEAL_SEL(k)))
@@ -650,16 +656,166 @@ __global__ __launch_bounds__(64 * WAVES) void k_seal_auth(const uint8_t* __restr
 
 static_assert(SEAL_AUTH_WAVES >= 4 && 16384 % SEAL_AUTH_WAVES == 0, "r8 is filled by the first 256 lanes");
 
+// ------------------------------------------------------------------ k_reseal_ctr
+// One pass from the ciphertext under one key to the ciphertext under another: c' = c ^ ks_old ^ ks_new,
+// where the two keystreams are xored before the ciphertext meets them, so no plaintext byte exists
+// even in a register, and the GHASH of c (the old tag) and of c' (the new one) run side by side.  The
+// pieces, the lanes' blocks and the partials are k_seal_ctr's; every source byte is loaded once and
+// every output byte stored once.
+//
+// What does not fit k_seal_ctr's shape: a second GHASH table set per wave
+// (SealLds at 16 waves is 153 KiB of 160) and a second key schedule (120 wave-uniform words are more
+// than the scalar file holds).  So a workgroup has RESEAL_WAVES = 8 waves, each with two table sets
+// (slot 2 wid: old, 2 wid + 1: new), and both schedules lie in LDS beside them: a round's four words
+// are one 16-byte read at a wave-uniform address (a broadcast, no bank conflict) next to the round's
+// 64 table lookups.  Four AES blocks (two blocks x two keys) are in flight per lane, which gives the
+// two waves a SIMD holds the independent LDS reads that four waves give k_seal_ctr.
+struct ResealLds {
+    uint32_t te[256][64];                     // as SealLds
+    uint32_t gt[2 * RESEAL_WAVES][256][4];    // [2 wave + side] Shoup 8-bit table of H^64
+    uint32_t g4[2 * RESEAL_WAVES][6][16][4];  // [2 wave + side][level][nibble] Shoup 4-bit tables of H^(2^k)
+    uint32_t r8[256], r4[16];
+    uint32_t rk[RESEAL_WAVES][2][60];         // [wave][side] AES-256 round keys
+};
+static_assert(sizeof(ResealLds) <= 160 * 1024, "one workgroup per CU");
+static_assert(RESEAL_WAVES >= 4 && 16384 % RESEAL_WAVES == 0, "te and r8 are filled by the first 256 lanes");
+
+// block g of the item: cin = the ciphertext at s (what the old tag covers), cout = cin ^ kx, stored
+// to d (what the new tag covers); both zero-padded past the item's end
+__device__ __forceinline__ void reseal_block(const uint8_t* s, uint8_t* d, uint64_t len, uint64_t g, const uint32_t kx[4],
+                                             G4& cin, G4& cout) {
+    const uint64_t at = 16 * g;
+    cin = auth_block(s, len, g);
+    uint32_t out[4] = {cin.w0 ^ kx[0], cin.w1 ^ kx[1], cin.w2 ^ kx[2], cin.w3 ^ kx[3]};
+    if (at + 16 <= len) {
+        *(uint4*)(d + at) = make_uint4(__builtin_bswap32(out[0]), __builtin_bswap32(out[1]), __builtin_bswap32(out[2]),
+                                       __builtin_bswap32(out[3]));
+    } else {
+        const uint32_t nb = (uint32_t)(len - at);
+        for (uint32_t b = 0; b < nb; b++) d[at + b] = (uint8_t)(out[b >> 2] >> (24 - 8 * (b & 3)));
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const int v = (int)nb - 4 * w;  // valid bytes of word w (big-endian)
+            out[w] &= v >= 4 ? ~0u : (v <= 0 ? 0u : ~0u << (32 - 8 * v));
+        }
+    }
+    cout = {out[0], out[1], out[2], out[3]};
+}
+
+// items: the geometry (src_off, len, dst_off, piece0; the old nonces); keys_o / keys_n: k_seal_prep's
+// output under the old and the new PRK (and nonces); parts_o / parts_n: a partial per piece each
+__global__ __launch_bounds__(64 * RESEAL_WAVES) void k_reseal_ctr(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                                  const SealItem* __restrict__ items, uint64_t n_items,
+                                                                  const SealKey* __restrict__ keys_o,
+                                                                  const SealKey* __restrict__ keys_n, uint64_t n_pieces,
+                                                                  uint32_t* __restrict__ parts_o,
+                                                                  uint32_t* __restrict__ parts_n) {
+    __shared__ __attribute__((aligned(16))) ResealLds L;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid < 256) {
+        const uint32_t t0 = aes_te0(aes_sbox(tid));
+        L.te[tid][0] = t0;
+        L.te[tid][32] = ror32(t0, 8);
+        G4 v = {0, 0, 0, tid};
+        for (int k = 0; k < 8; k++) {
+            v = gmulx(v);
+            if (k == 3 && tid < 16) L.r4[tid] = v.w0;
+        }
+        L.r8[tid] = v.w0;
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < 256 * 64; e += 64 * RESEAL_WAVES) {
+        const uint32_t row = e >> 6, col = e & 63;
+        if (col != 0 && col != 32) L.te[row][col] = L.te[row][col < 32 ? 0 : 32];
+    }
+    __syncthreads();
+    const uint32_t lane_off = (lane & 31) * 4;
+    const uint32_t so = 2 * wid, sn = 2 * wid + 1;
+
+    for (uint64_t p = (uint64_t)blockIdx.x * RESEAL_WAVES + wid; p < n_pieces; p += (uint64_t)gridDim.x * RESEAL_WAVES) {
+        // item owning piece p (items[].piece0 ascending), and the piece's blocks, as in k_seal_ctr
+        uint64_t lo = 0, hi = n_items;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (items[mid].piece0 <= p) lo = mid + 1;
+            else hi = mid;
+        }
+        const uint64_t ii = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(lo - 1));
+        const SealItem& it = items[ii];
+        const SealKey& Ko = keys_o[ii];
+        const SealKey& Kn = keys_n[ii];
+        const uint64_t len = it.len, m = (len + 15) / 16;
+        const uint64_t pi = p - it.piece0, np = (m + PIECE_BLOCKS - 1) / PIECE_BLOCKS;
+        const uint64_t first = m - (np - 1) * PIECE_BLOCKS;
+        const uint64_t b0 = pi == 0 ? 0 : first + (pi - 1) * PIECE_BLOCKS;
+        const uint32_t q = (uint32_t)(pi == 0 ? first : PIECE_BLOCKS);
+        if (lane < 60) {
+            L.rk[wid][0][lane] = Ko.rk[lane];
+            L.rk[wid][1][lane] = Kn.rk[lane];
+        }
+        ghash_wave_tables(L, Ko, so, lane);
+        ghash_wave_tables(L, Kn, sn, lane);  // its barrier publishes the round keys too
+
+        const uint8_t* s = src + it.src_off;
+        uint8_t* d = dst + it.dst_off;
+        const uint32_t S = (q + 63) / 64, pad = 64 * S - q;
+        G4 Xo = {0, 0, 0, 0}, Xn = {0, 0, 0, 0};
+        uint32_t r1o[4], r1n[4];
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            r1o[w] = Ko.R1[w];
+            r1n[w] = Kn.R1[w];
+        }
+        for (uint32_t j = 0; j < S; j += 2) {
+            const int32_t ra = (int32_t)(lane + 64 * j) - (int32_t)pad;  // >= -63; rb = ra + 64 >= 1
+            const uint64_t ga = b0 + (uint32_t)(ra < 0 ? 0 : ra), gb = b0 + (uint32_t)(ra + 64);
+            uint32_t ka[4], kb[4], na[4], nb[4];
+            // an offset the compiler cannot see through, taken per step: the round keys are read from
+            // LDS where a round uses them, not hoisted out of the loop into 120 registers
+            uint32_t zo = 0;
+            asm volatile("" : "+v"(zo));
+            const uint32_t* rko = L.rk[wid][0] + zo;
+            const uint32_t* rkn = L.rk[wid][1] + zo;
+            aes_ctr2(L, rko, r1o, lane_off, (uint32_t)(ga + 2), (uint32_t)(gb + 2), ka, kb);
+            aes_ctr2(L, rkn, r1n, lane_off, (uint32_t)(ga + 2), (uint32_t)(gb + 2), na, nb);
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                ka[w] ^= na[w];
+                kb[w] ^= nb[w];
+            }
+            G4 ci, co;
+            if (j) {
+                Xo = gmul_h64(L, Xo, so);
+                Xn = gmul_h64(L, Xn, sn);
+            }
+            if (ra >= 0) {
+                reseal_block(s, d, len, ga, ka, ci, co);
+                Xo = gxor(Xo, ci);
+                Xn = gxor(Xn, co);
+            }
+            if (j + 1 < S) {  // wave-uniform
+                Xo = gmul_h64(L, Xo, so);
+                Xn = gmul_h64(L, Xn, sn);
+                reseal_block(s, d, len, gb, kb, ci, co);
+                Xo = gxor(Xo, ci);
+                Xn = gxor(Xn, co);
+            }
+        }
+        Xo = ghash_wave_fold(L, Xo, so, lane);
+        Xn = ghash_wave_fold(L, Xn, sn, lane);
+        if (lane == 0) {
+            st4(parts_o + 4 * p, Xo);
+            st4(parts_n + 4 * p, Xn);
+        }
+        __builtin_amdgcn_wave_barrier();  // the tables and the round keys are rebuilt for the next piece
+    }
+}
+
 // ------------------------------------------------------------------ k_seal_tag
-template <bool DEC>
-__global__ __launch_bounds__(256) void k_seal_tag(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                  const SealItem* __restrict__ items, uint64_t n,
-                                                  const SealKey* __restrict__ keys, const uint32_t* __restrict__ parts,
-                                                  uint8_t* __restrict__ ok) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const SealItem& it = items[i];
-    const SealKey& K = keys[i];
+// the tag of one item from its pieces' partials: folded with H^PIECE_BLOCKS, the length block, E(J0)
+__device__ __forceinline__ void seal_tag_words(const SealItem& it, const SealKey& K, const uint32_t* __restrict__ parts,
+                                               uint32_t tw[4]) {
     const uint64_t len = it.len, m = (len + 15) / 16;
     const uint64_t np = (m + PIECE_BLOCKS - 1) / PIECE_BLOCKS;
     const G4 H = ld4(K.H);
@@ -673,7 +829,43 @@ __global__ __launch_bounds__(256) void k_seal_tag(const uint8_t* __restrict__ sr
     const G4 Lb = {0, 0, (uint32_t)(bits >> 32), (uint32_t)bits};
     G4 y = gmul_slow(gxor(gmul_slow(acc, H), Lb), H);
     y = gxor(y, ld4(K.E0));
-    const uint32_t tw[4] = {y.w0, y.w1, y.w2, y.w3};
+    tw[0] = y.w0; tw[1] = y.w1; tw[2] = y.w2; tw[3] = y.w3;
+}
+
+// k_seal_tag<true> and k_seal_tag<false> in one lane: the old tag is compared, and the new tag is
+// stored behind the new ciphertext where it matched and complemented where it did not, so an item
+// that was not authentic under the old key is not authentic under the new one either
+__global__ __launch_bounds__(256) void k_reseal_tag(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                    const SealItem* __restrict__ items, uint64_t n,
+                                                    const SealKey* __restrict__ keys_o, const SealKey* __restrict__ keys_n,
+                                                    const uint32_t* __restrict__ parts_o, const uint32_t* __restrict__ parts_n,
+                                                    uint8_t* __restrict__ ok) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const SealItem& it = items[i];
+    uint32_t to[4], tn[4];
+    seal_tag_words(it, keys_o[i], parts_o, to);
+    seal_tag_words(it, keys_n[i], parts_n, tn);
+    const uint8_t* t = src + it.src_off + it.len;
+    uint32_t diff = 0;
+    for (int b = 0; b < 16; b++) diff |= t[b] ^ (uint8_t)(to[b >> 2] >> (24 - 8 * (b & 3)));
+    const uint8_t flip = diff ? 0xff : 0;
+    uint8_t* u = dst + it.dst_off + it.len;
+    for (int b = 0; b < 16; b++) u[b] = (uint8_t)(tn[b >> 2] >> (24 - 8 * (b & 3))) ^ flip;
+    ok[i] = diff == 0;
+}
+
+template <bool DEC>
+__global__ __launch_bounds__(256) void k_seal_tag(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                  const SealItem* __restrict__ items, uint64_t n,
+                                                  const SealKey* __restrict__ keys, const uint32_t* __restrict__ parts,
+                                                  uint8_t* __restrict__ ok) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const SealItem& it = items[i];
+    const uint64_t len = it.len;
+    uint32_t tw[4];
+    seal_tag_words(it, keys[i], parts, tw);
     if (!DEC) {
         uint8_t* t = dst + it.dst_off + len;
         for (int b = 0; b < 16; b++) t[b] = (uint8_t)(tw[b >> 2] >> (24 - 8 * (b & 3)));
@@ -784,6 +976,23 @@ void launch_seal(hipStream_t st, bool dec, bool framed, const uint8_t* src, uint
     else
         hipLaunchKernelGGL(k_seal_tag<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, it, n, k,
                            parts, ok);
+}
+
+void launch_reseal(hipStream_t st, const uint8_t* src, uint8_t* dst, const SealItem* it_o, const SealItem* it_n, uint64_t n,
+                   const SealPads& pads_o, const SealPads& pads_n, SealKey* k_o, SealKey* k_n, uint64_t n_pieces,
+                   uint32_t* parts_o, uint32_t* parts_n, uint8_t* ok) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_seal_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, it_o, n, pads_o, k_o);
+    hipLaunchKernelGGL(k_seal_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, it_n, n, pads_n, k_n);
+    if (n_pieces) {
+        // a grid pass covers 16,384 pieces, as a pass of k_seal_ctr does
+        uint64_t grid = (n_pieces + RESEAL_WAVES - 1) / RESEAL_WAVES;
+        if (grid > 16384 / RESEAL_WAVES) grid = 16384 / RESEAL_WAVES;
+        hipLaunchKernelGGL(k_reseal_ctr, dim3((unsigned)grid), dim3(64 * RESEAL_WAVES), 0, st, src, dst, it_o, n, k_o, k_n,
+                           n_pieces, parts_o, parts_n);
+    }
+    hipLaunchKernelGGL(k_reseal_tag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, it_o, n, k_o, k_n, parts_o,
+                       parts_n, ok);
 }
 
 }  // namespace bw

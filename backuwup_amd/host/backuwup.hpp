@@ -698,6 +698,57 @@ private:
     size_t n_pf_, n_entries_, n_items_;
 };
 
+// ------------------------------------------------------------------ rekey (no counterpart in the reference)
+// A store under a new backup secret without a plaintext byte stored: store() reseals every header and
+// blob of an open Restore into a buffer with the same packfile table; reseal() does it to sealed items
+// in a host buffer.
+class Rekey {
+public:
+    struct Store {
+        std::vector<uint8_t> data;             // the new packfiles, at the session's offsets
+        std::vector<uint8_t> entry_status;     // BW_UNPACK_OK, _ETAG or _ERANGE per header entry
+        std::vector<uint8_t> packfile_status;  // the header's verdict per packfile
+    };
+    struct Items {
+        std::vector<uint8_t> data;  // output i: src_len[i] bytes at dst_off[i]
+        std::vector<uint8_t> ok;    // 1 where item i was authentic under the old PRK
+    };
+
+    static Store store(Context& ctx, Restore& session, const PackfileTable& t, size_t n_entries,
+                       const std::array<uint8_t, 32>& new_prk) {
+        Store r;
+        uint64_t end = 0;
+        for (const auto& f : t.tab) end = std::max<uint64_t>(end, f.offset + f.size);
+        r.data.resize(end + 1);
+        r.entry_status.resize(n_entries + 1);
+        r.packfile_status.resize(t.tab.size() + 1);
+        check(bw_rekey_store(session.get(), new_prk.data(), r.data.data(), r.entry_status.data(), r.packfile_status.data()),
+              ctx.get());
+        r.data.resize(end);
+        r.entry_status.resize(n_entries);
+        r.packfile_status.resize(t.tab.size());
+        return r;
+    }
+
+    // src_len includes the tag; infos holds info_len bytes per item, nonces 12; new_nonces empty = kept
+    static Items reseal(Context& ctx, const std::array<uint8_t, 32>& old_prk, const std::array<uint8_t, 32>& new_prk,
+                        const std::vector<uint8_t>& src, const std::vector<uint64_t>& src_off,
+                        const std::vector<uint64_t>& src_len, const std::vector<uint8_t>& infos, uint32_t info_len,
+                        const std::vector<uint8_t>& nonces, const std::vector<uint8_t>& new_nonces,
+                        const std::vector<uint64_t>& dst_off, uint64_t dst_size) {
+        Items r;
+        r.data.resize(dst_size + 1);
+        r.ok.resize(src_off.size() + 1);
+        check(bw_reseal(ctx.get(), old_prk.data(), new_prk.data(), src.data(), src_off.data(), src_len.data(), src_off.size(),
+                        infos.data(), info_len, nonces.data(), new_nonces.empty() ? nullptr : new_nonces.data(), r.data.data(),
+                        dst_off.data(), r.ok.data()),
+              ctx.get());
+        r.data.resize(dst_size);
+        r.ok.resize(src_off.size());
+        return r;
+    }
+};
+
 // ------------------------------------------------------------------ index files (blob_index.rs)
 using IndexEntry = std::pair<BlobHash, PackfileId>;
 

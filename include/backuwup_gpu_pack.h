@@ -41,6 +41,29 @@ int bw_seal(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* src, const uint64
 int bw_open(bw_ctx* ctx, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
             const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
             const uint8_t* nonces, uint8_t* dst, const uint64_t* dst_off, uint8_t* ok);
+/* Reseal: item i, sealed under old_prk with nonces[i], comes out sealed under new_prk with
+ * new_nonces[i] (NULL: the nonces are kept).  The tables are bw_open_device's: src_len[i] includes the
+ * tag (>= 16, else BW_EINVAL), and output i is src_len[i] bytes at d_dst + dst_off[i].  Where item i is
+ * authentic, output i is, byte for byte,
+ *   Aes256Gcm(HKDF(new_prk, info_i)).encrypt(new_nonce_i, open(old_prk, item_i)),
+ * and ok[i] (host) equals bw_open_device's ok[i] under old_prk for every input.
+ * An item whose old tag does not verify does not come out with a valid new tag (that would launder
+ * damage into an authentic blob): its ok[i] is 0, its ciphertext bytes are whatever the xor gives, and
+ * its 16 tag bytes are the bitwise complement of the tag that would verify, so it is rejected under
+ * the new key.
+ * The new ciphertext is c ^ keystream_old ^ keystream_new, the two keystreams xored first: no
+ * plaintext byte is stored to device or host memory.  Every source byte is read once and never
+ * written; nothing outside the output ranges and the context's scratch is written.  Output ranges
+ * must not overlap each other or a source range (BW_EINVAL, before anything is written).
+ * Synchronous. */
+int bw_reseal_device(bw_ctx* ctx, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* d_src,
+                     const uint64_t* src_off, const uint64_t* src_len, uint64_t n, const uint8_t* info,
+                     uint32_t info_len, const uint8_t* nonces, const uint8_t* new_nonces, uint8_t* d_dst,
+                     const uint64_t* dst_off, uint8_t* ok);
+/* Same over host buffers (only the output ranges are written; the plaintext exists on neither side). */
+int bw_reseal(bw_ctx* ctx, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* src,
+              const uint64_t* src_off, const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+              const uint8_t* nonces, const uint8_t* new_nonces, uint8_t* dst, const uint64_t* dst_off, uint8_t* ok);
 
 /* ---- packfiles and index files ----
  * Manager::write_packfiles + serialize_packfile (pack.rs:115-227): the queue of unique blobs
@@ -514,6 +537,27 @@ int bw_check_structure(bw_restore* session, uint8_t* entry_flags, uint8_t* item_
 #define BW_CHECK_AUTH 1u
 #define BW_CHECK_FULL 2u
 int bw_check_data(bw_restore* session, uint32_t mode, const uint8_t* select, uint8_t* status);
+
+/* ---- rekey: the store of an open restore session under a new secret ----
+ * The session holds the old PRK, the packfiles on the device, the entries and the ids.  d_out (device)
+ * receives the same packfile table -- the same offsets, sizes and ids -- with packfile p laid out as
+ *   u64 header_len || header resealed (info "header", nonce = id) || per entry: nonce copied || blob
+ *   resealed (info = the entry's hash)
+ * through bw_reseal_device's path, headers and blobs in one launch sequence: no plaintext is stored.
+ *   entry_status[e] (host, one byte per session entry): BW_UNPACK_OK or BW_UNPACK_ETAG (the output's
+ *     tag is then the complement of the valid one); BW_UNPACK_ERANGE for an entry that leaves its
+ *     packfile's blob section (it is never read).
+ *   packfile_status[p] (host): the header's verdict, BW_UNPACK_OK or BW_UNPACK_ETAG; BW_UNPACK_ERANGE
+ *     where 8 + header_len exceeds the packfile or header_len < 16 (the header is copied as it is).
+ * Every byte of a packfile that no in-range entry and no header covers (the length prefix, the nonces,
+ * trailing bytes of a blob section) is copied as it is.  Two in-range entries of one packfile whose
+ * ranges (nonce and sealed bytes) overlap: BW_EINVAL before anything is written.  d_out must not overlap
+ * the session's packfiles.  An empty session returns BW_OK.  Synchronous. */
+int bw_rekey_store_device(bw_restore* session, const uint8_t new_prk[32], uint8_t* d_out, uint8_t* entry_status,
+                          uint8_t* packfile_status);
+/* Same into a host buffer of the packfile table's extent: only the packfiles' ranges are written. */
+int bw_rekey_store(bw_restore* session, const uint8_t new_prk[32], uint8_t* out, uint8_t* entry_status,
+                   uint8_t* packfile_status);
 
 #ifdef __cplusplus
 }

@@ -501,6 +501,18 @@ pub mod ffi {
                                   stats: *mut bw_check_packfile_stat, counts: *mut bw_check_counts) -> c_int;
         pub fn bw_check_data(session: *mut bw_restore, mode: u32, select: *const u8, status: *mut u8) -> c_int;
 
+        pub fn bw_reseal_device(ctx: *mut bw_ctx, old_prk: *const u8, new_prk: *const u8, d_src: *const u8,
+                                src_off: *const u64, src_len: *const u64, n: u64, info: *const u8, info_len: u32,
+                                nonces: *const u8, new_nonces: *const u8, d_dst: *mut u8, dst_off: *const u64,
+                                ok: *mut u8) -> c_int;
+        pub fn bw_reseal(ctx: *mut bw_ctx, old_prk: *const u8, new_prk: *const u8, src: *const u8, src_off: *const u64,
+                         src_len: *const u64, n: u64, info: *const u8, info_len: u32, nonces: *const u8,
+                         new_nonces: *const u8, dst: *mut u8, dst_off: *const u64, ok: *mut u8) -> c_int;
+        pub fn bw_rekey_store_device(session: *mut bw_restore, new_prk: *const u8, d_out: *mut u8, entry_status: *mut u8,
+                                     packfile_status: *mut u8) -> c_int;
+        pub fn bw_rekey_store(session: *mut bw_restore, new_prk: *const u8, out: *mut u8, entry_status: *mut u8,
+                              packfile_status: *mut u8) -> c_int;
+
         pub fn bw_profile_enable(ctx: *mut bw_ctx, on: c_int) -> c_int;
         pub fn bw_profile_read(ctx: *mut bw_ctx, stage_ms: *mut f64, n_batches: *mut u64) -> c_int;
         pub fn bw_profile_intervals(ctx: *mut bw_ctx, stage: c_int, out: *mut f64, cap: u64, n: *mut u64) -> c_int;
