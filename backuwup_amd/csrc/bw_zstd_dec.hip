@@ -29,7 +29,7 @@ struct __attribute__((packed, aligned(1))) Vec16 {
 // The execution policy of a wave (see bw_zstd_dec_core.h).
 struct WaveExec {
     uint32_t lane;
-    const uint8_t* dirty;  // lowest output address stored since the last barrier (null: none)
+    zd::Hazard hz;  // what the wave stored since its last barrier
 
     template <class F>
     __device__ void for_streams(uint32_t n, F f) {
@@ -38,14 +38,11 @@ struct WaveExec {
     __device__ int any(int v) { return __any(v != 0) ? 1 : 0; }
     __device__ void sync() {
         __syncthreads();
-        dirty = nullptr;
-    }
-    __device__ void wrote(const uint8_t* d) {
-        if (!dirty) dirty = d;
+        hz.synced();
     }
     // d and s do not overlap
     __device__ void copy(uint8_t* d, const uint8_t* s, uint32_t n) {
-        wrote(d);
+        hz.wrote(d);
         if (n >= 256) {
             const uint32_t head = (uint32_t)(-(uintptr_t)d) & 15u;
             if (lane < head) d[lane] = s[lane];
@@ -61,19 +58,18 @@ struct WaveExec {
         for (uint32_t i = lane; i < n; i += 64) d[i] = s[i];
     }
     __device__ void fill(uint8_t* d, uint8_t b, uint32_t n) {
-        wrote(d);
+        hz.wrote(d);
         for (uint32_t i = lane; i < n; i += 64) d[i] = b;
     }
     // n bytes at d from d - off (off >= 1; the source may run into the bytes being written)
     __device__ void match(uint8_t* d, size_t off, uint32_t n) {
+        if (hz.must_wait(d, off, n)) sync();
         const uint8_t* s = d - off;
-        const size_t span = off < n ? off : n;  // source bytes that exist before this match
-        if (dirty && s + span > dirty) sync();
         if (off >= n) {
             copy(d, s, n);
             return;
         }
-        wrote(d);
+        hz.wrote(d);
         const uint32_t o = (uint32_t)off;  // < n <= 128 KiB + 2
         for (uint32_t i = lane; i < n; i += 64) d[i] = s[i % o];
     }
@@ -88,7 +84,7 @@ __global__ __launch_bounds__(64) void k_zd_frame(const uint8_t* __restrict__ src
     uint8_t* litbuf = lit + (uint64_t)blockIdx.x * ZD_LIT_STRIDE;
     for (uint64_t i = blockIdx.x; i < n; i += gridDim.x) {
         const ZdItem it = items[i];
-        WaveExec x{threadIdx.x, nullptr};
+        WaveExec x{threadIdx.x, {nullptr}};
         size_t got = 0;
         const int e = zd::decode_frame(src + it.src_off, (size_t)it.src_len, dst + it.dst_off, (size_t)it.dst_cap, &st,
                                        &sc, litbuf, &got, x);

@@ -622,6 +622,24 @@ ZD_FN int decode_frame(const uint8_t* src, size_t len, uint8_t* dst, size_t cap,
     return OK;
 }
 
+// Which matches must wait for the stores of a wide execution policy (the kernel's WaveExec; on the
+// host the checking policy of tests/cpp/zstd_dec_hazard.cpp, which holds the rule to what was
+// really stored).  The output grows upwards, so everything stored since the last barrier lies at or
+// above the first address stored since then.
+struct Hazard {
+    const uint8_t* dirty;  // lowest output address stored since the last barrier (null: none)
+    ZD_FN void synced() { dirty = nullptr; }
+    ZD_FN void wrote(const uint8_t* d) {
+        if (!dirty) dirty = d;
+    }
+    // a match of n bytes at d from d - off: does its source reach what was stored since the barrier?
+    ZD_FN bool must_wait(const uint8_t* d, size_t off, uint32_t n) const {
+        const uint8_t* s = d - off;
+        const size_t span = off < n ? off : n;  // source bytes that exist before this match
+        return dirty && s + span > dirty;
+    }
+};
+
 // The serial execution policy (host programs; also a device thread working alone).
 struct SerialExec {
     template <class F>

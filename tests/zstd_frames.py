@@ -306,14 +306,47 @@ def _sequences(buf, pos, end, tables, lit_regen):
     return r
 
 
-def classify(frame):
-    """One record per block of a magicless frame; ValueError if the frame is not consumed exactly."""
+def _frame_header(buf):
+    """Every form of the frame header (RFC 8878 3.1.1.1) -> (header fields, next pos).  Refused, as
+    the decoder refuses them: the reserved bit, the checksum flag, a non-zero dictionary id and a
+    window above 2^31."""
+    _need(len(buf) >= 1, "shorter than its header")
+    d = buf[0]
+    _need(d & 8 == 0, "reserved bit of the frame header descriptor")
+    _need(d & 4 == 0, "content checksum flag")
+    single, pos = bool(d & 0x20), 1
+    window_log = None
+    if not single:
+        _need(pos < len(buf), "missing window descriptor")
+        window_log = 10 + (buf[pos] >> 3)
+        _need(window_log <= 31, "window above 2^31")
+        pos += 1
+    did_width = (0, 1, 2, 4)[d & 3]
+    _need(pos + did_width <= len(buf), "dictionary id runs past the frame")
+    _need(not any(buf[pos:pos + did_width]), "non-zero dictionary id")
+    pos += did_width
+    fcs_width = (1 if single else 0, 2, 4, 8)[d >> 6]
+    _need(pos + fcs_width <= len(buf), "content size runs past the frame")
+    fcs = int.from_bytes(buf[pos:pos + fcs_width], "little") + (256 if fcs_width == 2 else 0) if fcs_width else None
+    return {"single_segment": single, "window_log": window_log, "did_width": did_width, "fcs_width": fcs_width,
+            "fcs": fcs}, pos + fcs_width
+
+
+def classify(frame, any_header=False):
+    """One record per block of a magicless frame; ValueError if the frame is not consumed exactly.
+    any_header=False: only the header this project's encoder writes (descriptor 0x00).  True: every
+    header form, its fields in each record's "header"; a content size must be the regenerated one."""
     buf = bytes(frame)
-    _need(len(buf) >= 2, "shorter than its header")
-    _need(buf[0] == 0, "frame header descriptor is not 0")
-    _need(buf[1] & 7 == 0 and (buf[1] >> 3) <= 12, "window descriptor outside 1 KiB..4 MiB powers of two")
-    window_log = 10 + (buf[1] >> 3)
-    pos, out, tables, have_tree = 2, [], {}, False
+    if any_header:
+        head, pos = _frame_header(buf)
+        window_log = head["window_log"]
+    else:
+        _need(len(buf) >= 2, "shorter than its header")
+        _need(buf[0] == 0, "frame header descriptor is not 0")
+        _need(buf[1] & 7 == 0 and (buf[1] >> 3) <= 12, "window descriptor outside 1 KiB..4 MiB powers of two")
+        window_log = 10 + (buf[1] >> 3)
+        head, pos = None, 2
+    out, tables, have_tree = [], {}, False
     while True:
         _need(pos + 3 <= len(buf), "missing block header")
         h = int.from_bytes(buf[pos:pos + 3], "little")
@@ -344,10 +377,14 @@ def classify(frame):
             rec["body"] = size
             pos = end
         _need(rec["regen"] <= BLOCK_MAX, "block regenerates more than 128 KiB")
+        if head is not None:
+            rec["header"] = head
         out.append(rec)
         if last:
             break
     _need(pos == len(buf), "%d bytes after the last block" % (len(buf) - pos))
+    if head is not None and head["fcs_width"]:
+        _need(head["fcs"] == sum(r["regen"] for r in out), "content size differs from the regenerated size")
     return out
 
 
@@ -418,6 +455,33 @@ FORMAT_CLASSES = (
     "long_offset", "of_code_ge20", "ll_code_35", "ml_code_52",
     "rep1", "rep2_at_ll0", "rep2", "rep3_at_ll0", "rep3", "rep1_minus_1",
 )
+
+
+# What a decoder must read beyond what this project's encoder writes: the header forms, the width
+# of the sequence count and of a raw / RLE literals header.  (The repeat-offset index of every
+# sequence -- codes 1, 2, 3, each with ll == 0 and ll > 0 -- and direct / FSE-coded Huffman weights
+# are the rep* and huf_weights_* names above.)
+HEADER_CLASSES = ("single_segment", "window_descriptor", "fcs_0", "fcs_1", "fcs_2", "fcs_4", "fcs_8",
+                  "dict_id_0", "dict_id_1", "dict_id_2", "dict_id_4")
+DECODER_CLASSES = FORMAT_CLASSES + HEADER_CLASSES + (
+    "nseq_header1", "nseq_header2", "nseq_header3",
+    "lit_raw_header1", "lit_raw_header2", "lit_raw_header3", "lit_rle_header1", "lit_rle_header2", "lit_rle_header3",
+)
+
+
+def decoder_classes(blocks):
+    """frame_classes plus the DECODER_CLASSES names, over the records of classify(frame, any_header=True)."""
+    c = frame_classes(blocks)
+    h = blocks[0]["header"]
+    c.add("single_segment" if h["single_segment"] else "window_descriptor")
+    c.add("fcs_%d" % h["fcs_width"])
+    c.add("dict_id_%d" % h["did_width"])
+    for b in blocks:
+        if b["type"] == "compressed":
+            c.add("nseq_header%d" % b["nseq_header"])
+            if b["lit_type"] in ("raw", "rle"):
+                c.add("lit_%s_header%d" % (b["lit_type"], b["lit_header"]))
+    return c
 
 
 def census(frames):
