@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BW_LIB") or os.path.join(HERE, "libbackuwup_amd.so")
 
 BW_OK, BW_EINVAL, BW_ENOSPC, BW_EHIP, BW_ENOMEM, BW_ECOLLISION, BW_ESTATE = 0, -1, -2, -3, -4, -5, -6
-BW_ECRYPTO, BW_EFORMAT, BW_ECOMM, BW_EAGAIN = -7, -8, -9, -10
+BW_ECRYPTO, BW_EFORMAT, BW_ECOMM, BW_EAGAIN, BW_ETOOFEW = -7, -8, -9, -10, -11
 BW_COMM_ID_BYTES = 128
 BW_COMM_DEFAULT_TIMEOUT_MS = 120000
 BW_ZSTD_LANES = 6  # include/backuwup_gpu.h: asynchronous zstd batches in flight per context
@@ -142,6 +142,15 @@ class BwCheckCounts(ctypes.Structure):
                 ("n_items_mismatch", ctypes.c_uint64), ("n_items_duplicate", ctypes.c_uint64),
                 ("n_packfiles_clean", ctypes.c_uint64)]
 
+
+class BwParityGroup(ctypes.Structure):
+    _fields_ = [("first_packfile", ctypes.c_uint64), ("k", ctypes.c_uint32), ("m", ctypes.c_uint32),
+                ("shard_len", ctypes.c_uint64), ("out_offset", ctypes.c_uint64)]
+
+
+BW_PARITY_OK, BW_PARITY_DAMAGED, BW_PARITY_REBUILT, BW_PARITY_REBUILT_BAD, BW_PARITY_LOST = 0, 1, 2, 3, 4
+# bw_internal.h: k_gf_matmul's row tile, bytes per wave task, and bytes per destination row of one grid pass
+GF_ROW_TILE, GF_WAVE_BYTES, GF_GRID_BYTES = 8, 2048, 1024 * 4 * 2048
 
 BW_TREE_FILE, BW_TREE_DIR = 0, 1
 BW_TREE_HAS_SIZE, BW_TREE_HAS_MTIME, BW_TREE_HAS_CTIME = 1, 2, 4
@@ -286,6 +295,20 @@ SIGNATURES = [
     ("bw_reseal", ctypes.c_int, [vp, vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, vp, u64p, u8p]),
     ("bw_rekey_store_device", ctypes.c_int, [vp, vp, vp, u8p, u8p]),
     ("bw_rekey_store", ctypes.c_int, [vp, vp, vp, u8p, u8p]),
+    ("bw_gf_matmul_device", ctypes.c_int, [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, u64p, u64p, vp, u64p,
+                                           ctypes.c_uint64]),
+    ("bw_gf_matmul", ctypes.c_int, [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, u64p, u64p, vp, u64p, ctypes.c_uint64]),
+    ("bw_parity_plan", ctypes.c_int, [u64p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                      ctypes.POINTER(BwParityGroup), ctypes.c_uint64, u64p, u64p]),
+    ("bw_parity_build_device", ctypes.c_int, [vp, vp, ctypes.POINTER(BwPackfile), ctypes.c_uint64,
+                                              ctypes.POINTER(BwParityGroup), ctypes.c_uint64, vp, ctypes.c_uint64, u8p]),
+    ("bw_parity_build", ctypes.c_int, [vp, vp, ctypes.POINTER(BwPackfile), ctypes.c_uint64,
+                                       ctypes.POINTER(BwParityGroup), ctypes.c_uint64, vp, ctypes.c_uint64, u8p]),
+    ("bw_parity_solve", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, u8p, ctypes.POINTER(ctypes.c_uint32),
+                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), u8p]),
+    ("bw_parity_repair_device", ctypes.c_int, [vp, ctypes.POINTER(BwParityGroup), u8p, vp, u64p, u64p, u8p, vp, u64p,
+                                               u8p]),
+    ("bw_parity_repair", ctypes.c_int, [vp, ctypes.POINTER(BwParityGroup), u8p, vp, u64p, u64p, u8p, vp, u64p, u8p]),
     ("bw_profile_enable", ctypes.c_int, [vp, ctypes.c_int]),
     ("bw_fastcdc_chunks_hashed", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint32, vp, ctypes.c_uint64, u64p, u64p]),

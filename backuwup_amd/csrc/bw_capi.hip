@@ -371,6 +371,7 @@ extern "C" const char* bw_strerror(int rc) {
         case BW_EFORMAT: return "malformed bincode data";
         case BW_ECOMM: return "the exchange transport failed (communicator aborted)";
         case BW_EAGAIN: return "the hash service could not take the call; retry through a context";
+        case BW_ETOOFEW: return "fewer shards present than the parity group has data shards";
         default: return "unknown error";
     }
 }
@@ -433,7 +434,7 @@ extern "C" void bw_destroy(bw_ctx* c) {
                      &c->data, &c->scratch, &c->ucnt, &c->ubtot, &c->seal_items, &c->seal_keys, &c->seal_parts,
                      &c->seal_ok, &c->seal_io, &c->pk_blobs, &c->pk_files, &c->pk_hdr, &c->pk_src, &c->pk_out,
                      &c->ix_io, &c->ix_tab, &c->ix_dig, &c->bk_blk, &c->bk_pack, &c->bk_v, &c->zs_io, &c->pk_stage,
-                     &c->ex_rbk, &c->ex_v, &c->ex_rv};
+                     &c->ex_rbk, &c->ex_v, &c->ex_rv, &c->gf_tab, &c->gf_io};
     for (auto& L : c->zs_lanes) {  // batches still in flight finish first
         if (L.th.joinable()) L.th.join();
         if (L.own_st) hipStreamDestroy(L.own_st);  // (lane 0's own stream leaked)

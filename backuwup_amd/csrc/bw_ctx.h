@@ -173,6 +173,9 @@ struct bw_ctx {
     hipEvent_t pk_done = nullptr;  // the host tables above reusable once this fired
     bool pk_pending = false;
 
+    // parity (bw_parity.hip): k_gf_matmul's job, coefficient and offset tables; host-call staging
+    DevBuf gf_tab, gf_io;
+
     // many small messages (tree blobs): pinned staging of the serialized bytes
     PinBuf msg_stage;
 

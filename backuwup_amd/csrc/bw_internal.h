@@ -239,6 +239,11 @@ void launch_seal(hipStream_t st, bool dec, bool framed, const uint8_t* src, uint
                  uint64_t n, const SealPads& pads, SealKey* keys, uint64_t n_pieces, uint32_t* parts, uint8_t* ok);
 uint32_t zstd_window_descriptor(uint64_t raw_len);
 
+// ------------------------------------------------------------------ parity (bw_parity.hip)
+constexpr int GF_ROW_TILE = 8;             // k_gf_matmul: destination rows accumulated per pass over the sources
+constexpr uint32_t GF_WAVE_BYTES = 2048;   // bytes of every destination row one wave task covers (16 per lane and step)
+constexpr uint32_t GF_GRID_BLOCKS = 1024;  // blocks of 4 waves per launch: a grid pass covers 4096 wave tasks
+
 // ------------------------------------------------------------------ host helpers
 // fn(lo, hi) over [0, n) on up to 16 threads: the host-side table work of million-item batches
 // (16 = this GPU's share of the box's cores).  `work` (default n) sizes the thread count; small

@@ -749,6 +749,97 @@ public:
     }
 };
 
+// ------------------------------------------------------------------ parity (no counterpart in the reference)
+// Reed-Solomon shards over a packfile table and repair from them: plan() groups the packfiles, build()
+// writes every parity shard and returns every shard's BLAKE3, solve() is the host Gauss-Jordan, repair()
+// rebuilds one group's missing or damaged shards; matmul() is the GF(2^8) primitive under both.
+class Parity {
+public:
+    struct Plan {
+        std::vector<bw_parity_group> groups;
+        uint64_t out_bytes = 0;
+    };
+    struct Built {
+        std::vector<uint8_t> parity;   // parity shard i of group g at groups[g].out_offset + i * shard_len
+        std::vector<uint8_t> digests;  // 32 bytes per shard: per group the data shards, then the parity shards
+    };
+    struct Solved {
+        std::vector<uint32_t> used, missing;
+        std::vector<uint8_t> matrix;  // missing.size() x k
+    };
+    struct Repaired {
+        std::vector<uint8_t> data;    // a rebuilt shard s: shard_len bytes at out_off[s]
+        std::vector<uint8_t> status;  // BW_PARITY_* per shard
+    };
+
+    static Plan plan(const std::vector<uint64_t>& sizes, uint32_t k, uint32_t m) {
+        Plan p;
+        uint64_t n = 0;
+        int rc = bw_parity_plan(sizes.data(), sizes.size(), k, m, nullptr, 0, &n, &p.out_bytes);
+        if (rc != BW_ENOSPC) check(rc);
+        p.groups.resize(n + 1);
+        check(bw_parity_plan(sizes.data(), sizes.size(), k, m, p.groups.data(), n, &n, &p.out_bytes));
+        p.groups.resize(n);
+        return p;
+    }
+
+    static Built build(Context& ctx, const PackfileTable& t, const Plan& p) {
+        Built b;
+        size_t shards = 0;
+        for (const auto& g : p.groups) shards += g.k + g.m;
+        b.parity.resize(p.out_bytes + 1);
+        b.digests.resize(32 * shards + 1);
+        check(bw_parity_build(ctx.get(), t.data.data(), t.tab.data(), t.tab.size(), p.groups.data(), p.groups.size(),
+                              b.parity.data(), p.out_bytes, b.digests.data()),
+              ctx.get());
+        b.parity.resize(p.out_bytes);
+        b.digests.resize(32 * shards);
+        return b;
+    }
+
+    // throws Error with rc BW_ETOOFEW where fewer than k shards are present
+    static Solved solve(uint32_t k, uint32_t m, const std::vector<uint8_t>& present) {
+        Solved s;
+        s.used.resize(k + 1);
+        s.missing.resize(k + m + 1);
+        s.matrix.resize((size_t)(k + m) * k + 1);
+        uint32_t n = 0;
+        check(bw_parity_solve(k, m, present.data(), s.used.data(), s.missing.data(), &n, s.matrix.data()));
+        s.used.resize(k);
+        s.missing.resize(n);
+        s.matrix.resize((size_t)n * k);
+        return s;
+    }
+
+    // digests: (k + m) x 32 as build() returned them for the group, or empty for none
+    static Repaired repair(Context& ctx, const bw_parity_group& g, const std::vector<uint8_t>& present,
+                           const std::vector<uint8_t>& shards, const std::vector<uint64_t>& shard_off,
+                           const std::vector<uint64_t>& shard_size, const std::vector<uint8_t>& digests,
+                           const std::vector<uint64_t>& out_off, uint64_t out_size) {
+        Repaired r;
+        r.data.resize(out_size + 1);
+        r.status.resize(g.k + g.m + 1);
+        check(bw_parity_repair(ctx.get(), &g, present.data(), shards.data(), shard_off.data(), shard_size.data(),
+                               digests.empty() ? nullptr : digests.data(), r.data.data(), out_off.data(), r.status.data()),
+              ctx.get());
+        r.data.resize(out_size);
+        r.status.resize(g.k + g.m);
+        return r;
+    }
+
+    // row r of the result: len bytes at dst_off[r]; matrix is dst_off.size() x src_off.size(), row-major
+    static std::vector<uint8_t> matmul(Context& ctx, const std::vector<uint8_t>& matrix, const std::vector<uint8_t>& src,
+                                       const std::vector<uint64_t>& src_off, const std::vector<uint64_t>& src_len,
+                                       const std::vector<uint64_t>& dst_off, uint64_t len, uint64_t dst_size) {
+        std::vector<uint8_t> out(dst_size + 1);
+        check(bw_gf_matmul(ctx.get(), matrix.data(), (uint32_t)dst_off.size(), (uint32_t)src_off.size(), src.data(),
+                           src_off.data(), src_len.data(), out.data(), dst_off.data(), len),
+              ctx.get());
+        out.resize(dst_size);
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------ index files (blob_index.rs)
 using IndexEntry = std::pair<BlobHash, PackfileId>;
 

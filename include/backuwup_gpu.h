@@ -49,10 +49,11 @@ enum {
     BW_ECRYPTO = -7,    /* an AES-GCM tag did not verify (PackfileError::CryptoError)           */
     BW_EFORMAT = -8,    /* bincode deserialization failed (PackfileError::SerializationError)   */
     BW_ECOMM = -9,      /* the exchange transport failed (RCCL, or the caller's host all-to-all) */
-    BW_EAGAIN = -10     /* bw_blake3_hash_dropin_device only: the device's hash service could not
+    BW_EAGAIN = -10,    /* bw_blake3_hash_dropin_device only: the device's hash service could not
                            take this call (message over BW_COALESCE_MAX_MSG, service unavailable,
                            or no digest within its bound); nothing was changed, retry the message
                            through a context (bw_blake3_hash_many)                                 */
+    BW_ETOOFEW = -11    /* bw_parity_solve: fewer than k of a parity group's k + m shards are present */
 };
 
 /* fastcdc::v2020 size bounds (asserted by FastCDC::with_level).  avg > max passes those asserts, but

@@ -559,6 +559,91 @@ int bw_rekey_store_device(bw_restore* session, const uint8_t new_prk[32], uint8_
 int bw_rekey_store(bw_restore* session, const uint8_t new_prk[32], uint8_t* out, uint8_t* entry_status,
                    uint8_t* packfile_status);
 
+/* ---- parity: Reed-Solomon shards over packfiles, and repair from them ----
+ * The reference has no redundancy: one lost packfile loses every file with a chunk in it.  A parity
+ * group is k data shards (packfiles, byte for byte as stored, zero-extended to the group's shard_len)
+ * and m parity shards over GF(2^8) with the polynomial 0x11d and the generator 2:
+ *   P_i[b] = XOR_j mul(C[i][j], D_j[b]),  C[i][j] = inv(i ^ (m + j)),  0 <= i < m, 0 <= j < k, b < shard_len
+ * (a Cauchy matrix: any k of the k + m shards rebuild the rest; C[i][j] does not depend on k, so a
+ * short last group uses the leading columns).  1 <= k, 1 <= m, k + m <= 256. */
+
+/* The primitive: dst_r[b] = XOR_c mul(matrix[r * cols + c], src_c[b]) for b < len, r < rows (k_gf_matmul,
+ * one launch).  Source c is d_src[src_off[c] ..] at any alignment and reads as zero at and beyond
+ * src_len[c]; destination r is d_dst[dst_off[r] .. dst_off[r] + len).  d_dst and every dst_off must be
+ * 16-byte aligned, rows >= 1 and 1 <= cols <= 255, else BW_EINVAL.  Every byte of every destination
+ * range is written (a zero row writes zeros), nothing else is, and no source byte at or beyond its
+ * src_len is read.  Destinations must not overlap each other or a source.  matrix and the tables are
+ * host arrays.  Synchronous. */
+int bw_gf_matmul_device(bw_ctx* ctx, const uint8_t* matrix, uint32_t rows, uint32_t cols, const uint8_t* d_src,
+                        const uint64_t* src_off, const uint64_t* src_len, uint8_t* d_dst, const uint64_t* dst_off,
+                        uint64_t len);
+/* Same over host buffers: the sources are uploaded and only the destination ranges come back. */
+int bw_gf_matmul(bw_ctx* ctx, const uint8_t* matrix, uint32_t rows, uint32_t cols, const uint8_t* src,
+                 const uint64_t* src_off, const uint64_t* src_len, uint8_t* dst, const uint64_t* dst_off, uint64_t len);
+
+typedef struct bw_parity_group {
+    uint64_t first_packfile; /* position in the packfile table of the group's first data shard        */
+    uint32_t k, m;           /* data shards (consecutive packfiles), parity shards                      */
+    uint64_t shard_len;      /* the largest member's size rounded up to 16                              */
+    uint64_t out_offset;     /* parity shard i lies at out_offset + i * shard_len of the parity buffer  */
+} bw_parity_group;
+
+/* Host only.  Groups take consecutive packfiles in table order, k per group, the last one the
+ * remainder; offsets are 16-aligned and back to back, *out_bytes their end.  A size of 0, k or m of 0
+ * or k + m > 256 -> BW_EINVAL; cap too small -> BW_ENOSPC with *n_groups and *out_bytes set. */
+int bw_parity_plan(const uint64_t* sizes, uint64_t n_pf, uint32_t k, uint32_t m, bw_parity_group* out, uint64_t cap,
+                   uint64_t* n_groups, uint64_t* out_bytes);
+
+/* Every parity shard of every group into d_out (device, 16-byte aligned, out_cap bytes), all groups in
+ * one k_gf_matmul launch over d_packfiles (device; packfile p at packfiles[p].offset, .size bytes).
+ * digests (host): the BLAKE3 of every shard, 32 bytes each, group by group, data shards then parity
+ * shards (32 * (n_pf + sum of m) bytes for a plan that covers the table); data shards are hashed at
+ * their true size, parity shards at shard_len, through the device hashing of the verified unpack chain.
+ * A group that leaves the table or the output, a shard_len below a member's size or no multiple of 16,
+ * a misaligned out_offset -> BW_EINVAL before anything is written.  Synchronous. */
+int bw_parity_build_device(bw_ctx* ctx, const uint8_t* d_packfiles, const bw_packfile* packfiles, uint64_t n_pf,
+                           const bw_parity_group* groups, uint64_t n_groups, uint8_t* d_out, uint64_t out_cap,
+                           uint8_t* digests);
+/* Same over host buffers (data of the packfile table's extent, out of out_cap bytes). */
+int bw_parity_build(bw_ctx* ctx, const uint8_t* data, const bw_packfile* packfiles, uint64_t n_pf,
+                    const bw_parity_group* groups, uint64_t n_groups, uint8_t* out, uint64_t out_cap, uint8_t* digests);
+
+/* Host only.  present[s] != 0: shard s of the k + m (data shards first) is at hand.  used[0 .. k): the
+ * inputs, every present data shard and then the lowest-numbered present parity shards; missing[0 ..
+ * *n_missing): the absent shards, ascending (room for k + m entries); matrix (*n_missing x k, row-major,
+ * room for (k + m) * k bytes): row r times the inputs in the order of `used` is shard missing[r], data
+ * and parity alike (Gauss-Jordan inverse over GF(2^8), times the Cauchy rows for missing parity).
+ * Fewer than k present -> BW_ETOOFEW with missing and *n_missing set. */
+int bw_parity_solve(uint32_t k, uint32_t m, const uint8_t* present, uint32_t* used, uint32_t* missing,
+                    uint32_t* n_missing, uint8_t* matrix);
+
+/* Per-shard status of bw_parity_repair. */
+enum {
+    BW_PARITY_OK = 0,          /* present (and, with digests, authentic); nothing written               */
+    BW_PARITY_DAMAGED = 1,     /* present, its digest differs: not used as an input, rebuilt, and good   */
+    BW_PARITY_REBUILT = 2,     /* missing, rebuilt (with digests: and its digest agrees)                 */
+    BW_PARITY_REBUILT_BAD = 3, /* rebuilt, but its digest differs or bytes beyond its size are not zero  */
+    BW_PARITY_LOST = 4         /* more than m shards missing or damaged: nothing was written             */
+};
+
+/* One group.  Shard s (data shards 0 .. k, then parity) lies, where present[s] != 0, at
+ * d_shards[shard_off[s] ..] with shard_size[s] bytes: a packfile's true size (<= shard_len) or shard_len
+ * for a parity shard, else BW_EINVAL.  digests (host, (k + m) x 32 as bw_parity_build returned them, may
+ * be NULL): present shards are hashed first and one whose digest differs is demoted to missing, so a
+ * damaged survivor is never an input; rebuilt shards are hashed at shard_size.  Every missing or demoted
+ * shard s is written at d_out[out_off[s] ..], shard_len bytes (16-byte aligned; the caller keeps
+ * shard_size[s] of them), by one k_gf_matmul launch; a rebuilt data shard whose bytes beyond shard_size
+ * are not zero is BW_PARITY_REBUILT_BAD even without digests.  status[s] (host): BW_PARITY_*.  With more
+ * than m shards gone the call returns BW_OK, every gone shard is BW_PARITY_LOST and nothing is written.
+ * Synchronous. */
+int bw_parity_repair_device(bw_ctx* ctx, const bw_parity_group* group, const uint8_t* present, const uint8_t* d_shards,
+                            const uint64_t* shard_off, const uint64_t* shard_size, const uint8_t* digests, uint8_t* d_out,
+                            const uint64_t* out_off, uint8_t* status);
+/* Same over host buffers: only the rebuilt shards' ranges of out are written (shard_len bytes each). */
+int bw_parity_repair(bw_ctx* ctx, const bw_parity_group* group, const uint8_t* present, const uint8_t* shards,
+                     const uint64_t* shard_off, const uint64_t* shard_size, const uint8_t* digests, uint8_t* out,
+                     const uint64_t* out_off, uint8_t* status);
+
 #ifdef __cplusplus
 }
 #endif

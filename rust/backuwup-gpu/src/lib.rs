@@ -274,6 +274,23 @@ pub mod ffi {
     pub const BW_CHECK_E_ORDER: u8 = 2;
     pub const BW_CHECK_E_UNINDEXED: u8 = 4;
     pub const BW_CHECK_E_SHADOWED: u8 = 8;
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_parity_group {
+        pub first_packfile: u64,
+        pub k: u32,
+        pub m: u32,
+        pub shard_len: u64,
+        pub out_offset: u64,
+    }
+
+    pub const BW_ETOOFEW: c_int = -11;
+    pub const BW_PARITY_OK: u8 = 0;
+    pub const BW_PARITY_DAMAGED: u8 = 1;
+    pub const BW_PARITY_REBUILT: u8 = 2;
+    pub const BW_PARITY_REBUILT_BAD: u8 = 3;
+    pub const BW_PARITY_LOST: u8 = 4;
+
     pub const BW_CHECK_SKIPPED: u8 = 32;
     pub const BW_CHECK_IDUPLICATE: u8 = 33;
     pub const BW_CHECK_AUTH: u32 = 1;
@@ -512,6 +529,29 @@ pub mod ffi {
                                      packfile_status: *mut u8) -> c_int;
         pub fn bw_rekey_store(session: *mut bw_restore, new_prk: *const u8, out: *mut u8, entry_status: *mut u8,
                               packfile_status: *mut u8) -> c_int;
+
+        pub fn bw_gf_matmul_device(ctx: *mut bw_ctx, matrix: *const u8, rows: u32, cols: u32, d_src: *const u8,
+                                   src_off: *const u64, src_len: *const u64, d_dst: *mut u8, dst_off: *const u64,
+                                   len: u64) -> c_int;
+        pub fn bw_gf_matmul(ctx: *mut bw_ctx, matrix: *const u8, rows: u32, cols: u32, src: *const u8,
+                            src_off: *const u64, src_len: *const u64, dst: *mut u8, dst_off: *const u64,
+                            len: u64) -> c_int;
+        pub fn bw_parity_plan(sizes: *const u64, n_pf: u64, k: u32, m: u32, out: *mut bw_parity_group, cap: u64,
+                              n_groups: *mut u64, out_bytes: *mut u64) -> c_int;
+        pub fn bw_parity_build_device(ctx: *mut bw_ctx, d_packfiles: *const u8, packfiles: *const bw_packfile, n_pf: u64,
+                                      groups: *const bw_parity_group, n_groups: u64, d_out: *mut u8, out_cap: u64,
+                                      digests: *mut u8) -> c_int;
+        pub fn bw_parity_build(ctx: *mut bw_ctx, data: *const u8, packfiles: *const bw_packfile, n_pf: u64,
+                               groups: *const bw_parity_group, n_groups: u64, out: *mut u8, out_cap: u64,
+                               digests: *mut u8) -> c_int;
+        pub fn bw_parity_solve(k: u32, m: u32, present: *const u8, used: *mut u32, missing: *mut u32,
+                               n_missing: *mut u32, matrix: *mut u8) -> c_int;
+        pub fn bw_parity_repair_device(ctx: *mut bw_ctx, group: *const bw_parity_group, present: *const u8,
+                                       d_shards: *const u8, shard_off: *const u64, shard_size: *const u64,
+                                       digests: *const u8, d_out: *mut u8, out_off: *const u64, status: *mut u8) -> c_int;
+        pub fn bw_parity_repair(ctx: *mut bw_ctx, group: *const bw_parity_group, present: *const u8, shards: *const u8,
+                                shard_off: *const u64, shard_size: *const u64, digests: *const u8, out: *mut u8,
+                                out_off: *const u64, status: *mut u8) -> c_int;
 
         pub fn bw_profile_enable(ctx: *mut bw_ctx, on: c_int) -> c_int;
         pub fn bw_profile_read(ctx: *mut bw_ctx, stage_ms: *mut f64, n_batches: *mut u64) -> c_int;
