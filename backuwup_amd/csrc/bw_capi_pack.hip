@@ -27,147 +27,36 @@ using namespace bw;
 
 // ------------------------------------------------------------------ blob sealing (§8f row 3)
 // compress_encrypt_blob's HKDF key + AES-256-GCM (pack.rs:70-80) and the inverse
-// (unpack.rs:58-63, blob_index.rs:185-191); kernels in bw_seal.hip.
+// (unpack.rs:58-63, blob_index.rs:185-191), and reseal: items under prk become the same plaintexts
+// under new_prk without a plaintext byte stored anywhere; kernels in bw_seal.hip.
 
-// raw_len (sealing only, may be null): item i's plaintext is the zstd store frame of raw_len[i]
-// source bytes at d_src + src_off[i], built inside k_seal_ctr; src_len[i] is the frame length.
-// auth (with dec): the tags are checked and no plaintext is written; d_dst and dst_off are not used.
-static int seal_submit(bw_ctx* c, bool dec, const uint8_t* prk, const uint8_t* d_src, const uint64_t* src_off,
-                       const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
-                       const uint8_t* nonces, uint8_t* d_dst, const uint64_t* dst_off, uint8_t* ok,
-                       const uint64_t* raw_len = nullptr, bool auth = false) {
-    if (!c || !prk || info_len > BW_SEAL_MAX_INFO) return BW_EINVAL;
-    if (n && (!d_src || !src_off || !src_len || !nonces || (info_len && !info))) return BW_EINVAL;
-    if (n && !auth && (!d_dst || !dst_off)) return BW_EINVAL;
-    if (dec && n && !ok) return BW_EINVAL;
-    hipSetDevice(c->device);
-    if (!n) return BW_OK;
-    if (dec)
-        for (uint64_t i = 0; i < n; i++)
-            if (src_len[i] < 16) return BW_EINVAL;  // shorter than the tag: decrypt_in_place fails
-    if (!c->seal_done) HIPCHK(c, hipEventCreateWithFlags(&c->seal_done, hipEventDisableTiming));
-    if (c->seal_pending) {
-        hipEventSynchronize(c->seal_done);
-        c->seal_pending = false;
-    }
-    const size_t bytes = n * sizeof(SealItem);
-    if (int rc = ensure_host(c, c->seal_stage, bytes)) return rc;
-    SealItem* it = (SealItem*)c->seal_stage.p;
-    std::vector<uint64_t> piece0(n);
-    uint64_t pieces = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        piece0[i] = pieces;
-        pieces += seal_pieces(dec ? src_len[i] - 16 : src_len[i]);
-    }
-    parallel_ranges(n, [&](uint64_t lo, uint64_t hi) {
-        for (uint64_t i = lo; i < hi; i++) {
-            const uint64_t len = dec ? src_len[i] - 16 : src_len[i];
-            seal_fill_item(&it[i], src_off[i], len, auth ? 0 : dst_off[i], piece0[i], nonces + 12 * i,
-                           info + (uint64_t)info_len * i, info_len);
-            if (raw_len) {
-                it[i].raw_len = (uint32_t)raw_len[i];
-                it[i].wd = zstd_window_descriptor(raw_len[i]);
-            }
-        }
-    });
-    if (int rc = ensure(c, c->seal_items, bytes)) return rc;
-    if (int rc = ensure(c, c->seal_keys, n * sizeof(SealKey))) return rc;
-    if (int rc = ensure(c, c->seal_parts, (pieces + 1) * 16)) return rc;
-    if (dec)
-        if (int rc = ensure(c, c->seal_ok, n)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->seal_items.p, it, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->seal_done, c->stream));
-    c->seal_pending = true;
-    SealPads pads;
-    seal_pads(prk, &pads);
-    launch_seal(c->stream, dec, raw_len != nullptr, d_src, d_dst, P<SealItem>(c->seal_items), n, pads,
-                P<SealKey>(c->seal_keys), pieces,
-                P<uint32_t>(c->seal_parts), dec ? P<uint8_t>(c->seal_ok) : nullptr, auth);
-    HIPCHK(c, hipGetLastError());
-    if (dec) {
-        HIPCHK(c, hipMemcpyAsync(ok, c->seal_ok.p, n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return BW_OK;
+// One call's worth of items.  Every entry point of the family fills one and hands it to seal_submit.
+struct SealJob {
+    SealMode mode = SealMode::Seal;
+    const uint8_t* prk = nullptr;
+    const uint8_t* new_prk = nullptr;  // reseal: mode is Open (the source carries tags, ok is written),
+                                       // and what is written is the ciphertext || tag under new_prk
+    const uint8_t* d_src = nullptr;
+    const uint64_t* src_off = nullptr;
+    const uint64_t* src_len = nullptr;  // Seal: plaintext bytes; SealFramed: frame bytes; else ciphertext + tag
+    uint64_t n = 0;
+    const uint8_t* info = nullptr;  // n rows of info_len bytes
+    uint32_t info_len = 0;
+    const uint32_t* info_lens = nullptr;  // the bytes of row i that count (null: info_len for all)
+    const uint8_t* nonces = nullptr;
+    const uint8_t* new_nonces = nullptr;  // reseal (null: the nonces are kept)
+    uint8_t* d_dst = nullptr;             // not used by Auth
+    const uint64_t* dst_off = nullptr;
+    uint8_t* ok = nullptr;                // host, n bytes: Open, Auth and reseal
+    const uint64_t* raw_len = nullptr;    // SealFramed: item i's plaintext is the zstd store frame of raw_len[i]
+                                          // source bytes at d_src + src_off[i], built inside k_seal_ctr
+};
+
+// bytes item i leaves at dst_off[i]
+static uint64_t seal_out_len(const SealJob& j, uint64_t i) {
+    if (j.new_prk) return j.src_len[i];
+    return j.mode == SealMode::Open ? j.src_len[i] - 16 : j.src_len[i] + 16;
 }
-
-extern "C" int bw_seal_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
-                              const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
-                              const uint8_t* nonces, uint8_t* d_dst, const uint64_t* dst_off) {
-    return seal_submit(c, false, prk, d_src, src_off, src_len, n, info, info_len, nonces, d_dst, dst_off, nullptr);
-}
-
-extern "C" int bw_open_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
-                              const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
-                              const uint8_t* nonces, uint8_t* d_dst, const uint64_t* dst_off, uint8_t* ok) {
-    return seal_submit(c, true, prk, d_src, src_off, src_len, n, info, info_len, nonces, d_dst, dst_off, ok);
-}
-
-// bw_open_device's verdicts without its plaintext: k_seal_auth recomputes each tag from the ciphertext
-extern "C" int bw_auth_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
-                              const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
-                              const uint8_t* nonces, uint8_t* ok) {
-    return seal_submit(c, true, prk, d_src, src_off, src_len, n, info, info_len, nonces, nullptr, nullptr, ok, nullptr, true);
-}
-
-// the source is uploaded; nothing but ok comes back
-extern "C" int bw_auth(bw_ctx* c, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
-                       const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len, const uint8_t* nonces,
-                       uint8_t* ok) {
-    if (!c || !prk || (n && (!src || !src_off || !src_len))) return BW_EINVAL;
-    hipSetDevice(c->device);
-    uint64_t s_end = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        if (src_len[i] < 16) return BW_EINVAL;
-        s_end = std::max(s_end, src_off[i] + src_len[i]);
-    }
-    if (int rc = ensure(c, c->seal_io, s_end + 16)) return rc;
-    if (s_end) HIPCHK(c, hipMemcpyAsync(c->seal_io.p, src, s_end, hipMemcpyHostToDevice, c->stream));
-    return bw_auth_device(c, prk, P<uint8_t>(c->seal_io), src_off, src_len, n, info, info_len, nonces, ok);
-}
-
-// Host-buffer forms: both buffers go through one device staging area ([src | dst]).
-static int seal_host(bw_ctx* c, bool dec, const uint8_t* prk, const uint8_t* src, const uint64_t* src_off,
-                     const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
-                     const uint8_t* nonces, uint8_t* dst, const uint64_t* dst_off, uint8_t* ok) {
-    if (!c || (n && (!src || !src_off || !src_len || !dst || !dst_off))) return BW_EINVAL;
-    hipSetDevice(c->device);
-    uint64_t s_end = 0, d_end = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        if (dec && src_len[i] < 16) return BW_EINVAL;
-        s_end = std::max(s_end, src_off[i] + src_len[i]);
-        d_end = std::max(d_end, dst_off[i] + (dec ? src_len[i] - 16 : src_len[i] + 16));
-    }
-    const uint64_t d_base = (s_end + 255) & ~255ull;
-    if (int rc = ensure(c, c->seal_io, d_base + d_end + 16)) return rc;
-    uint8_t* io = P<uint8_t>(c->seal_io);
-    if (s_end) HIPCHK(c, hipMemcpyAsync(io, src, s_end, hipMemcpyHostToDevice, c->stream));
-    int rc = seal_submit(c, dec, prk, io, src_off, src_len, n, info, info_len, nonces, io + d_base, dst_off, ok);
-    if (rc) return rc;
-    // copy back only the written ranges (the caller's gaps stay untouched)
-    for (uint64_t i = 0; i < n; i++) {
-        const uint64_t len = dec ? src_len[i] - 16 : src_len[i] + 16;
-        if (len) HIPCHK(c, hipMemcpyAsync(dst + dst_off[i], io + d_base + dst_off[i], len, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BW_OK;
-}
-
-extern "C" int bw_seal(bw_ctx* c, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
-                       const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
-                       const uint8_t* nonces, uint8_t* dst, const uint64_t* dst_off) {
-    return seal_host(c, false, prk, src, src_off, src_len, n, info, info_len, nonces, dst, dst_off, nullptr);
-}
-
-extern "C" int bw_open(bw_ctx* c, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
-                       const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
-                       const uint8_t* nonces, uint8_t* dst, const uint64_t* dst_off, uint8_t* ok) {
-    return seal_host(c, true, prk, src, src_off, src_len, n, info, info_len, nonces, dst, dst_off, ok);
-}
-
-// ------------------------------------------------------------------ reseal
-// Items under old_prk become the same plaintexts under new_prk (and new nonces) without a plaintext
-// byte stored anywhere: kernels k_reseal_ctr and k_reseal_tag in bw_seal.hip.
 
 // true when an output range meets another output range or a source range (addresses a + off)
 static bool reseal_overlap(const uint8_t* src, const uint64_t* src_off, const uint8_t* dst, const uint64_t* dst_off,
@@ -190,65 +79,201 @@ static bool reseal_overlap(const uint8_t* src, const uint64_t* src_off, const ui
     return false;
 }
 
-int bw_reseal_items(bw_ctx* c, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* d_src,
-                    const uint64_t* src_off, const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
-                    const uint32_t* info_lens, const uint8_t* nonces, const uint8_t* new_nonces, uint8_t* d_dst,
-                    const uint64_t* dst_off, uint8_t* ok) {
-    if (!c || !old_prk || !new_prk || info_len > BW_SEAL_MAX_INFO) return BW_EINVAL;
-    if (n && (!d_src || !src_off || !src_len || !nonces || (info_len && !info) || !d_dst || !dst_off || !ok)) return BW_EINVAL;
+// Validates the job, builds its item table (two where a reseal changes the nonces: they differ in
+// nothing else), stages it and launches.  Sealing returns without synchronising; whatever writes ok
+// synchronises and copies it back.
+static int seal_submit(bw_ctx* c, const SealJob& j) {
+    const uint64_t n = j.n;
+    const bool reseal = j.new_prk != nullptr, auth = j.mode == SealMode::Auth;
+    const bool dec = j.mode == SealMode::Open || auth;  // the source carries tags
+    if (!c || !j.prk || j.info_len > BW_SEAL_MAX_INFO) return BW_EINVAL;
+    if (n && (!j.d_src || !j.src_off || !j.src_len || !j.nonces || (j.info_len && !j.info))) return BW_EINVAL;
+    if (n && !auth && (!j.d_dst || !j.dst_off)) return BW_EINVAL;
+    if (dec && n && !j.ok) return BW_EINVAL;
     hipSetDevice(c->device);
     if (!n) return BW_OK;
-    for (uint64_t i = 0; i < n; i++)
-        if (src_len[i] < 16 || (info_lens && info_lens[i] > info_len)) return BW_EINVAL;
-    if (reseal_overlap(d_src, src_off, d_dst, dst_off, src_len, n)) {
+    for (uint64_t i = 0; i < n; i++) {
+        if (dec && j.src_len[i] < 16) return BW_EINVAL;  // shorter than the tag: decrypt_in_place fails
+        if (j.info_lens && j.info_lens[i] > j.info_len) return BW_EINVAL;
+    }
+    if (reseal && reseal_overlap(j.d_src, j.src_off, j.d_dst, j.dst_off, j.src_len, n)) {
         c->err = "reseal: an output range overlaps another output range or a source range";
         return BW_EINVAL;
     }
     if (!c->seal_done) HIPCHK(c, hipEventCreateWithFlags(&c->seal_done, hipEventDisableTiming));
-    if (c->seal_pending) {
+    if (c->seal_pending) {  // the pinned stage is reusable once the previous call's upload has run
         hipEventSynchronize(c->seal_done);
         c->seal_pending = false;
     }
-    // two item tables only where the nonces change: they differ in nothing else
-    const uint64_t sides = new_nonces ? 2 : 1;
+    const uint64_t tables = reseal && j.new_nonces ? 2 : 1, sides = reseal ? 2 : 1;
     const size_t bytes = n * sizeof(SealItem);
-    if (int rc = ensure_host(c, c->seal_stage, sides * bytes)) return rc;
+    if (int rc = ensure_host(c, c->seal_stage, tables * bytes)) return rc;
     SealItem* it = (SealItem*)c->seal_stage.p;
     std::vector<uint64_t> piece0(n);
     uint64_t pieces = 0;
     for (uint64_t i = 0; i < n; i++) {
         piece0[i] = pieces;
-        pieces += seal_pieces(src_len[i] - 16);
+        pieces += seal_pieces(dec ? j.src_len[i] - 16 : j.src_len[i]);
     }
     parallel_ranges(n, [&](uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; i++) {
-            const uint32_t il = info_lens ? info_lens[i] : info_len;
-            seal_fill_item(&it[i], src_off[i], src_len[i] - 16, dst_off[i], piece0[i], nonces + 12 * i,
-                           info + (uint64_t)info_len * i, il);
-            if (new_nonces)
-                seal_fill_item(&it[n + i], src_off[i], src_len[i] - 16, dst_off[i], piece0[i], new_nonces + 12 * i,
-                               info + (uint64_t)info_len * i, il);
+            const uint64_t len = dec ? j.src_len[i] - 16 : j.src_len[i];
+            const uint8_t* info = j.info + (uint64_t)j.info_len * i;
+            const uint32_t il = j.info_lens ? j.info_lens[i] : j.info_len;
+            seal_fill_item(&it[i], j.src_off[i], len, auth ? 0 : j.dst_off[i], piece0[i], j.nonces + 12 * i, info, il);
+            if (tables == 2)
+                seal_fill_item(&it[n + i], j.src_off[i], len, j.dst_off[i], piece0[i], j.new_nonces + 12 * i, info, il);
+            if (j.mode == SealMode::SealFramed) {
+                it[i].raw_len = (uint32_t)j.raw_len[i];
+                it[i].wd = zstd_window_descriptor(j.raw_len[i]);
+            }
         }
     });
     const size_t part_bytes = (pieces + 1) * 16;
-    if (int rc = ensure(c, c->seal_items, sides * bytes)) return rc;
-    if (int rc = ensure(c, c->seal_keys, 2 * n * sizeof(SealKey))) return rc;
-    if (int rc = ensure(c, c->seal_parts, 2 * part_bytes)) return rc;
-    if (int rc = ensure(c, c->seal_ok, n)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->seal_items.p, it, sides * bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = ensure(c, c->seal_items, tables * bytes)) return rc;
+    if (int rc = ensure(c, c->seal_keys, sides * n * sizeof(SealKey))) return rc;
+    if (int rc = ensure(c, c->seal_parts, sides * part_bytes)) return rc;
+    if (dec)
+        if (int rc = ensure(c, c->seal_ok, n)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->seal_items.p, it, tables * bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->seal_done, c->stream));
     c->seal_pending = true;
-    SealPads pads_o, pads_n;
-    seal_pads(old_prk, &pads_o);
-    seal_pads(new_prk, &pads_n);
+    SealPads pads, pads_n;
+    seal_pads(j.prk, &pads);
     const SealItem* d_it = P<SealItem>(c->seal_items);
-    launch_reseal(c->stream, d_src, d_dst, d_it, new_nonces ? d_it + n : d_it, n, pads_o, pads_n, P<SealKey>(c->seal_keys),
-                  P<SealKey>(c->seal_keys) + n, pieces, P<uint32_t>(c->seal_parts),
-                  P<uint32_t>(c->seal_parts) + part_bytes / 4, P<uint8_t>(c->seal_ok));
+    if (reseal) {
+        seal_pads(j.new_prk, &pads_n);
+        launch_reseal(c->stream, j.d_src, j.d_dst, d_it, d_it + (tables - 1) * n, n, pads, pads_n, P<SealKey>(c->seal_keys),
+                      P<SealKey>(c->seal_keys) + n, pieces, P<uint32_t>(c->seal_parts),
+                      P<uint32_t>(c->seal_parts) + part_bytes / 4, P<uint8_t>(c->seal_ok));
+    } else {
+        launch_seal(c->stream, j.mode, j.d_src, j.d_dst, d_it, n, pads, P<SealKey>(c->seal_keys), pieces,
+                    P<uint32_t>(c->seal_parts), dec ? P<uint8_t>(c->seal_ok) : nullptr);
+    }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(ok, c->seal_ok.p, n, hipMemcpyDeviceToHost, c->stream));
+    if (dec) {
+        HIPCHK(c, hipMemcpyAsync(j.ok, c->seal_ok.p, n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return BW_OK;
+}
+
+// The job's host buffers staged in the device area seal_io as [src | 256-aligned dst] (no dst for
+// Auth): the source is uploaded, and the job is pointed at the device copies.
+static int seal_stage_io(bw_ctx* c, SealJob& j, const uint8_t* src, uint8_t* dst) {
+    const bool out = j.mode != SealMode::Auth, tagged = j.mode != SealMode::Seal;
+    if (!c || (j.n && (!src || !j.src_off || !j.src_len || (out && (!dst || !j.dst_off))))) return BW_EINVAL;
+    hipSetDevice(c->device);
+    uint64_t s_end = 0, d_end = 0;
+    for (uint64_t i = 0; i < j.n; i++) {
+        if (tagged && j.src_len[i] < 16) return BW_EINVAL;
+        s_end = std::max(s_end, j.src_off[i] + j.src_len[i]);
+        if (out) d_end = std::max(d_end, j.dst_off[i] + seal_out_len(j, i));
+    }
+    const uint64_t d_base = (s_end + 255) & ~255ull;
+    if (int rc = ensure(c, c->seal_io, d_base + d_end + 16)) return rc;
+    uint8_t* io = P<uint8_t>(c->seal_io);
+    if (s_end) HIPCHK(c, hipMemcpyAsync(io, src, s_end, hipMemcpyHostToDevice, c->stream));
+    j.d_src = io;
+    j.d_dst = out ? io + d_base : nullptr;
+    return BW_OK;
+}
+
+// only the written ranges come back (the caller's gaps stay untouched), then the stream is drained
+static int seal_fetch_io(bw_ctx* c, const SealJob& j, uint8_t* dst) {
+    for (uint64_t i = 0; i < j.n; i++)
+        if (const uint64_t len = seal_out_len(j, i))
+            HIPCHK(c, hipMemcpyAsync(dst + j.dst_off[i], j.d_dst + j.dst_off[i], len, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BW_OK;
+}
+
+// Host-buffer forms: staged, submitted, fetched.  A reseal's ranges are checked where the caller
+// holds them too: the staged copies never overlap across src and dst.
+static int seal_host(bw_ctx* c, SealJob j, const uint8_t* src, uint8_t* dst) {
+    if (int rc = seal_stage_io(c, j, src, dst)) return rc;
+    if (j.new_prk && j.n && reseal_overlap(src, j.src_off, dst, j.dst_off, j.src_len, j.n)) {
+        c->err = "reseal: an output range overlaps another output range or a source range";
+        return BW_EINVAL;
+    }
+    if (int rc = seal_submit(c, j)) return rc;
+    return j.d_dst ? seal_fetch_io(c, j, dst) : BW_OK;
+}
+
+static SealJob seal_job(SealMode mode, const uint8_t* prk, const uint64_t* src_off, const uint64_t* src_len, uint64_t n,
+                        const uint8_t* info, uint32_t info_len, const uint8_t* nonces, const uint64_t* dst_off, uint8_t* ok) {
+    SealJob j;
+    j.mode = mode;
+    j.prk = prk;
+    j.src_off = src_off;
+    j.src_len = src_len;
+    j.n = n;
+    j.info = info;
+    j.info_len = info_len;
+    j.nonces = nonces;
+    j.dst_off = dst_off;
+    j.ok = ok;
+    return j;
+}
+
+extern "C" int bw_seal_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
+                              const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                              const uint8_t* nonces, uint8_t* d_dst, const uint64_t* dst_off) {
+    SealJob j = seal_job(SealMode::Seal, prk, src_off, src_len, n, info, info_len, nonces, dst_off, nullptr);
+    j.d_src = d_src;
+    j.d_dst = d_dst;
+    return seal_submit(c, j);
+}
+
+extern "C" int bw_open_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
+                              const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                              const uint8_t* nonces, uint8_t* d_dst, const uint64_t* dst_off, uint8_t* ok) {
+    SealJob j = seal_job(SealMode::Open, prk, src_off, src_len, n, info, info_len, nonces, dst_off, ok);
+    j.d_src = d_src;
+    j.d_dst = d_dst;
+    return seal_submit(c, j);
+}
+
+// bw_open_device's verdicts without its plaintext: k_seal_auth recomputes each tag from the ciphertext
+extern "C" int bw_auth_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
+                              const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                              const uint8_t* nonces, uint8_t* ok) {
+    SealJob j = seal_job(SealMode::Auth, prk, src_off, src_len, n, info, info_len, nonces, nullptr, ok);
+    j.d_src = d_src;
+    return seal_submit(c, j);
+}
+
+// the source is uploaded; nothing but ok comes back
+extern "C" int bw_auth(bw_ctx* c, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
+                       const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len, const uint8_t* nonces,
+                       uint8_t* ok) {
+    return seal_host(c, seal_job(SealMode::Auth, prk, src_off, src_len, n, info, info_len, nonces, nullptr, ok), src, nullptr);
+}
+
+extern "C" int bw_seal(bw_ctx* c, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
+                       const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                       const uint8_t* nonces, uint8_t* dst, const uint64_t* dst_off) {
+    return seal_host(c, seal_job(SealMode::Seal, prk, src_off, src_len, n, info, info_len, nonces, dst_off, nullptr), src, dst);
+}
+
+extern "C" int bw_open(bw_ctx* c, const uint8_t prk[32], const uint8_t* src, const uint64_t* src_off,
+                       const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                       const uint8_t* nonces, uint8_t* dst, const uint64_t* dst_off, uint8_t* ok) {
+    return seal_host(c, seal_job(SealMode::Open, prk, src_off, src_len, n, info, info_len, nonces, dst_off, ok), src, dst);
+}
+
+int bw_reseal_items(bw_ctx* c, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* d_src,
+                    const uint64_t* src_off, const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
+                    const uint32_t* info_lens, const uint8_t* nonces, const uint8_t* new_nonces, uint8_t* d_dst,
+                    const uint64_t* dst_off, uint8_t* ok) {
+    if (!new_prk) return BW_EINVAL;
+    SealJob j = seal_job(SealMode::Open, old_prk, src_off, src_len, n, info, info_len, nonces, dst_off, ok);
+    j.new_prk = new_prk;
+    j.info_lens = info_lens;
+    j.new_nonces = new_nonces;
+    j.d_src = d_src;
+    j.d_dst = d_dst;
+    return seal_submit(c, j);
 }
 
 extern "C" int bw_reseal_device(bw_ctx* c, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* d_src,
@@ -263,35 +288,12 @@ extern "C" int bw_reseal_device(bw_ctx* c, const uint8_t old_prk[32], const uint
 extern "C" int bw_reseal(bw_ctx* c, const uint8_t old_prk[32], const uint8_t new_prk[32], const uint8_t* src,
                          const uint64_t* src_off, const uint64_t* src_len, uint64_t n, const uint8_t* info, uint32_t info_len,
                          const uint8_t* nonces, const uint8_t* new_nonces, uint8_t* dst, const uint64_t* dst_off, uint8_t* ok) {
-    if (!c || (n && (!src || !src_off || !src_len || !dst || !dst_off))) return BW_EINVAL;
-    hipSetDevice(c->device);
-    uint64_t s_end = 0, d_end = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        if (src_len[i] < 16) return BW_EINVAL;
-        s_end = std::max(s_end, src_off[i] + src_len[i]);
-        d_end = std::max(d_end, dst_off[i] + src_len[i]);
-    }
-    if (n && reseal_overlap(src, src_off, dst, dst_off, src_len, n)) {
-        c->err = "reseal: an output range overlaps another output range or a source range";
-        return BW_EINVAL;
-    }
-    const uint64_t d_base = (s_end + 255) & ~255ull;
-    if (int rc = ensure(c, c->seal_io, d_base + d_end + 16)) return rc;
-    uint8_t* io = P<uint8_t>(c->seal_io);
-    if (s_end) HIPCHK(c, hipMemcpyAsync(io, src, s_end, hipMemcpyHostToDevice, c->stream));
-    if (int rc = bw_reseal_device(c, old_prk, new_prk, io, src_off, src_len, n, info, info_len, nonces, new_nonces, io + d_base,
-                                  dst_off, ok))
-        return rc;
-    for (uint64_t i = 0; i < n; i++)
-        HIPCHK(c, hipMemcpyAsync(dst + dst_off[i], io + d_base + dst_off[i], src_len[i], hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BW_OK;
+    if (!new_prk) return BW_EINVAL;
+    SealJob j = seal_job(SealMode::Open, old_prk, src_off, src_len, n, info, info_len, nonces, dst_off, ok);
+    j.new_prk = new_prk;
+    j.new_nonces = new_nonces;
+    return seal_host(c, j, src, dst);
 }
-
-// ------------------------------------------------------------------ packfiles (§8f row 4)
-// Manager::write_packfiles / serialize_packfile (pack.rs:115-227); kernels in bw_pack.hip.
-
-static uint32_t varint_len(uint64_t v) { return v < 251 ? 1 : (v < (1ull << 16) ? 3 : (v < (1ull << 32) ? 5 : 9)); }
 
 // ------------------------------------------------------------------ zstd level 3
 
@@ -425,6 +427,11 @@ extern "C" uint64_t bw_zstd_store_size(uint64_t len) {
     const uint64_t nb = len ? (len + ZSTD_BLOCK - 1) / ZSTD_BLOCK : 1;
     return 2 + 3 * nb + len;
 }
+
+// ------------------------------------------------------------------ packfiles (§8f row 4)
+// Manager::write_packfiles / serialize_packfile (pack.rs:115-227); kernels in bw_pack.hip.
+
+static uint32_t varint_len(uint64_t v) { return v < 251 ? 1 : (v < (1ull << 16) ? 3 : (v < (1ull << 32) ? 5 : 9)); }
 
 static uint64_t sealed_len_of(uint64_t payload, uint32_t flags) {
     return (flags & BW_PACK_ZSTD_STORE ? bw_zstd_store_size(payload) : payload) + BW_SEAL_TAG_BYTES;
@@ -667,14 +674,19 @@ static int pack_submit(bw_ctx* c, const uint8_t* prk, const uint8_t* d_src, cons
     HIPCHK(c, hipGetLastError());
     // every blob: derive_backup_key(hash) + AES-GCM(nonce) of its payload (its store frame, built
     // while it is encrypted) into its place behind its nonce
-    if (int rc = seal_submit(c, false, prk, d_src, s_off.data(), s_len.data(), n, hashes, 32, nonces, d_out,
-                             d_off.data(), nullptr, store ? src_len : nullptr))
-        return rc;
+    SealJob blobs = seal_job(store ? SealMode::SealFramed : SealMode::Seal, prk, s_off.data(), s_len.data(), n, hashes, 32,
+                             nonces, d_off.data(), nullptr);
+    blobs.d_src = d_src;
+    blobs.d_dst = d_out;
+    blobs.raw_len = store ? src_len : nullptr;
+    if (int rc = seal_submit(c, blobs)) return rc;
     // every header: derive_backup_key(b"header") + AES-GCM(packfile id) behind the length prefix
     std::vector<uint8_t> info(npf * 6);
     for (uint64_t p = 0; p < npf; p++) memcpy(&info[6 * p], "header", 6);
-    return seal_submit(c, false, prk, P<uint8_t>(c->pk_hdr), h_off.data(), h_len.data(), npf, info.data(), 6, ids,
-                       d_out, h_dst.data(), nullptr);
+    SealJob headers = seal_job(SealMode::Seal, prk, h_off.data(), h_len.data(), npf, info.data(), 6, ids, h_dst.data(), nullptr);
+    headers.d_src = P<uint8_t>(c->pk_hdr);
+    headers.d_dst = d_out;
+    return seal_submit(c, headers);
 }
 
 extern "C" int bw_pack_build_device(bw_ctx* c, const uint8_t prk[32], const uint8_t* d_src, const uint64_t* src_off,
@@ -874,9 +886,11 @@ extern "C" int bw_index_load_files(bw_ctx* c, const uint8_t prk[32], const uint8
     uint8_t* io = P<uint8_t>(c->ix_io);
     HIPCHK(c, hipMemcpyAsync(io, data, end, hipMemcpyHostToDevice, c->stream));
     std::vector<uint8_t> ok(nf);
-    if (int rc = seal_submit(c, true, prk, io, src_off.data(), src_len.data(), nf, info.data(), 5, nonces.data(),
-                             io + pt_base, pt_off.data(), ok.data()))
-        return rc;
+    SealJob j = seal_job(SealMode::Open, prk, src_off.data(), src_len.data(), nf, info.data(), 5, nonces.data(), pt_off.data(),
+                         ok.data());
+    j.d_src = io;
+    j.d_dst = io + pt_base;
+    if (int rc = seal_submit(c, j)) return rc;
     for (uint64_t f = 0; f < nf; f++)
         if (!ok[f]) {
             if (bad_file) *bad_file = f;
@@ -1044,9 +1058,10 @@ extern "C" int bw_unpack_headers(bw_ctx* c, const uint8_t prk[32], const uint8_t
     for (uint64_t p = 0; p < npf; p++)
         HIPCHK(c, hipMemcpyAsync(io + src_off[p], data + pf[p].offset + 8, src_len[p], hipMemcpyHostToDevice, c->stream));
     std::vector<uint8_t> ok(npf);
-    if (int rc = seal_submit(c, true, prk, io, src_off.data(), src_len.data(), npf, info.data(), 6, ids, io + pt_base,
-                             pt_off.data(), ok.data()))
-        return rc;
+    SealJob j = seal_job(SealMode::Open, prk, src_off.data(), src_len.data(), npf, info.data(), 6, ids, pt_off.data(), ok.data());
+    j.d_src = io;
+    j.d_dst = io + pt_base;
+    if (int rc = seal_submit(c, j)) return rc;
     for (uint64_t p = 0; p < npf; p++)
         if (!ok[p]) return fail(p, BW_ECRYPTO, "header failed authentication");
     // count, then gather
@@ -1136,9 +1151,11 @@ int bw::unpack_blobs_core(bw_ctx* c, const uint8_t* prk, const uint8_t* d_pf, co
     HIPCHK(c, hipMemcpyAsync(nonces.data(), stg + nonce_base, 12 * m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (uint64_t k = 0; k < m; k++) memcpy(&hashes[32 * k], entries[idx[k]].hash, 32);
-    if (int rc = seal_submit(c, true, prk, d_pf, s_off.data(), s_len.data(), m, hashes.data(), 32, nonces.data(), stg,
-                             f_off.data(), ok.data()))
-        return rc;
+    SealJob j = seal_job(SealMode::Open, prk, s_off.data(), s_len.data(), m, hashes.data(), 32, nonces.data(), f_off.data(),
+                         ok.data());
+    j.d_src = d_pf;
+    j.d_dst = stg;
+    if (int rc = seal_submit(c, j)) return rc;
     // frames whose tag verified -> blobs
     std::vector<uint64_t> z_idx, z_off, z_len, z_dst, z_cap;
     for (uint64_t k = 0; k < m; k++) {

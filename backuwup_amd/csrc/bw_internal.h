@@ -216,7 +216,7 @@ struct SealItem {
     uint32_t info_len;
     uint8_t info[56];
     uint32_t raw_len, wd;  // store-framed items: the plaintext is the zstd store frame of raw_len
-                           // source bytes with window descriptor wd (launch_seal(framed = true))
+                           // source bytes with window descriptor wd (SealMode::SealFramed, bw_seal.h)
 };
 
 struct SealKey {
@@ -233,6 +233,9 @@ void seal_pads(const uint8_t prk[32], SealPads* pads);
 uint64_t seal_pieces(uint64_t len);  // k_seal_ctr wave tasks of an item of len bytes
 void seal_fill_item(SealItem* it, uint64_t src_off, uint64_t len, uint64_t dst_off, uint64_t piece0,
                     const uint8_t nonce[12], const uint8_t* info, uint32_t info_len);
+// No code calls this one any more: launch_seal(st, SealMode, ...) in bw_seal.h is the entry point, and
+// this declaration (with its one-line forwarder in bw_seal.hip) goes away in the change that next
+// re-stamps the PMC evidence, since this header's code is part of the profiled source digest.
 // dec = false: dst = ciphertext || tag; dec = true: dst = plaintext, ok[i] = tag verified
 // framed (sealing only): item plaintexts are zstd store frames built on the fly from the source
 void launch_seal(hipStream_t st, bool dec, bool framed, const uint8_t* src, uint8_t* dst, const SealItem* items,

@@ -1,18 +1,26 @@
-// bw_seal.h -- the authenticate-only mode of sealing and reseal (bw_seal.hip), declared apart from
-// bw_internal.h: they serve check and rekey, which are off the chunk -> hash -> dedup path
-// (backuwup_amd/build.py OFF_PATH).
+// bw_seal.h -- the launchers of bw_seal.hip: seal, open and authenticate through one launch_seal, and
+// reseal.  Declared apart from bw_internal.h, whose code is part of the profiled hot path's source
+// digest (backuwup_amd/build.py OFF_PATH); the item, key and pad types stay there.
 #pragma once
 #include "bw_internal.h"
 
 namespace bw {
 
+// What launch_seal does with the items (k_seal_prep first, k_seal_tag last, in every mode):
+enum class SealMode {
+    Seal,        // dst = ciphertext || tag (k_seal_ctr<false, false>)
+    SealFramed,  // Seal, the plaintext being the zstd store frame of the item's raw_len source bytes, built
+                 // while it is encrypted (k_seal_ctr<false, true>)
+    Open,        // src = ciphertext || tag, dst = plaintext, ok[i] = tag verified (k_seal_ctr<true, false>)
+    Auth,        // Open's ok without its plaintext: GHASH only (k_seal_auth); dst is not used
+};
+
 constexpr int SEAL_AUTH_WAVES = 8;  // k_seal_auth: waves per workgroup (5.5 KiB of GHASH tables each)
 
-// launch_seal with its third mode.  auth (with dec): the tags are checked and nothing else is
-// written: k_seal_prep, then k_seal_auth (GHASH only) in place of k_seal_ctr<true, false>, then
-// k_seal_tag<true>; dst is not used.  auth = false is launch_seal as bw_internal.h declares it.
-void launch_seal(hipStream_t st, bool dec, bool framed, const uint8_t* src, uint8_t* dst, const SealItem* items,
-                 uint64_t n, const SealPads& pads, SealKey* keys, uint64_t n_pieces, uint32_t* parts, uint8_t* ok, bool auth);
+// items[i].len is the plaintext's length in every mode; n_pieces the sum of seal_pieces over them;
+// parts holds 16 bytes per piece; ok (n bytes) is written by Open and Auth only.
+void launch_seal(hipStream_t st, SealMode mode, const uint8_t* src, uint8_t* dst, const SealItem* items, uint64_t n,
+                 const SealPads& pads, SealKey* keys, uint64_t n_pieces, uint32_t* parts, uint8_t* ok);
 
 constexpr int RESEAL_WAVES = 8;  // k_reseal_ctr: waves per workgroup (two GHASH table sets and two key schedules each)
 
