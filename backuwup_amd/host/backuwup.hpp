@@ -1017,10 +1017,13 @@ public:
                         }
                     }
                     std::vector<uint64_t> offs(hi - lo), lens(file_len.begin() + lo, file_len.begin() + hi);
+                    // every chunk but a file's last is >= min(2 * (min / 2), max) bytes, as in process_files
+                    const uint32_t s0 = 2 * (p_.min_size / 2);
+                    const uint64_t mc = s0 < p_.max_size ? s0 : p_.max_size;
                     uint64_t cap = 1;
                     for (size_t i = lo; i < hi; i++) {
                         offs[i - lo] = file_off[i] - a;
-                        cap += file_len[i] / (p_.min_size ? p_.min_size : 1) + 2;
+                        cap += file_len[i] / (mc ? mc : 1) + 2;
                     }
                     bw_ctx* c = ctx_[r]->get();
                     uint64_t t = 0, got = 0;

@@ -162,6 +162,29 @@ int main() {
                 printf(" %d\n", (int)b.is_dup);
             }
         }
+        // ---- odd min: every chunk but a file's last may be 2 * (min / 2) = 64 bytes, shorter than
+        // min = 65.  Byte 248's gear value passes avg = 256's mask_s on its own, so a file of that
+        // byte is cut at every first tested position: 20,000 bytes give 313 chunks, more than
+        // 20,000 / 65 + 2.  One such file per rank (four ranks on device 0), results in one line each.
+        try {
+            bw_params q;
+            bw_params_default(&q);
+            q.min_size = 65;
+            q.avg_size = 256;
+            q.max_size = 1024;
+            q.small_file_threshold = 256;
+            const std::vector<uint8_t> flat(4 * 20000, 248);
+            NodeSession odd({0, 0, 0, 0}, false, 1u << 14, &q);
+            auto blobs = odd.process_files(flat.data(), {0, 20000, 40000, 60000}, {20000, 20000, 20000, 20000});
+            for (const auto& b : blobs) {
+                printf("nso %llu %llu %llu %llu ", (unsigned long long)b.file, (unsigned long long)b.offset,
+                       (unsigned long long)b.length, (unsigned long long)b.gear_hash);
+                for (auto x : b.digest) printf("%02x", x);
+                printf(" %d\n", (int)b.is_dup);
+            }
+        } catch (const Error& e) {
+            printf("nso-error rc=%d %s\n", e.rc, e.what());
+        }
         // ---- the drop-in pool over the device list [0, 0]: 8 threads, small messages (home device's
         // service) and a few over 64 KiB (a pooled context), every digest printed
         Pool pool({0, 0}, 2);

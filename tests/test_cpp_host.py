@@ -108,6 +108,19 @@ def test_cpp_mirror_parity(tmp_path, oracle):
                  bytes(w["digest"]).hex(), int(w["is_dup"])), (bi, k)
             k += 1
     assert k == len(ns) and sum(int(x[-1]) for x in ns) > 0
+    # odd min (65): chunks of 2 * (min / 2) = 64 bytes, more of them than file_len / min + 2; one
+    # file per rank, against one oracle index
+    assert not [l for l in out if l.startswith("nso-error")], [l for l in out if l.startswith("nso-error")]
+    flat = np.full(80000, 248, np.uint8)
+    want = oracle.process_files(flat, [0, 20000, 40000, 60000], [20000] * 4, 65, 256, 1024, small_threshold=256,
+                                index=oracle.Index())
+    assert len(want) == 4 * 313 > 4 * (20000 // 65 + 2) + 4 and int((want["length"] == 64).sum()) == 4 * 312
+    nso = [l.split() for l in out if l.startswith("nso ")]
+    assert len(nso) == len(want)
+    for (_, f, o, ln, gh, d, dup), w in zip(nso, want):
+        assert (int(f), int(o), int(ln), int(gh), d, int(dup)) == \
+            (int(w["file"]), int(w["offset"]), int(w["length"]), int(w["gear_hash"]), bytes(w["digest"]).hex(),
+             int(w["is_dup"])), (f, o)
     # the drop-in pool over [0, 0]: every digest equal to the oracle's
     ph = [l.split() for l in out if l.startswith("ph ")]
     assert len(ph) == 400
