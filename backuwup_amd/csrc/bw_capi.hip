@@ -11,29 +11,22 @@
 //   * one dedup index (bw_index) can be shared by several contexts on several streams: every
 //     index operation waits for the index's previous operation (an event chain), so the batches of
 //     one backup session are gated in submission order whichever stream runs them.
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <functional>
 #include <mutex>
 #include <string>
-#include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/backuwup_gpu.h"
 #include "bw_device.h"
 #include "bw_internal.h"
-#include "bw_tables.inc"
 
 using namespace bw;
-
-static const uint64_t H_MASKS[26] = BW_MASKS_INIT;
 
 #include "bw_ctx.h"
 
@@ -84,43 +77,6 @@ void free_host(PinBuf& b) {
     if (b.p) hipHostFree(b.p);
     b.p = nullptr;
     b.cap = 0;
-}
-
-static int make_masks(uint32_t mn, uint32_t av, uint32_t mx, Masks* mk) {
-    // FastCDC::with_level asserts (fastcdc 3.0.3 v2020) -> BW_EINVAL instead of a panic.
-    if (mn < BW_MINIMUM_MIN || mn > BW_MINIMUM_MAX) return BW_EINVAL;
-    if (av < BW_AVERAGE_MIN || av > BW_AVERAGE_MAX) return BW_EINVAL;
-    if (mx < BW_MAXIMUM_MIN || mx > BW_MAXIMUM_MAX) return BW_EINVAL;
-    // avg > max passes the crate's asserts, but then cut() keeps center = avg past remaining = max:
-    // its first loop reads beyond max (a cut there makes a chunk longer than max) and, where the
-    // source ends first, indexes out of bounds -- a panic, on most inputs (oracle/bw_oracle.c
-    // ORC_CUT_PANIC restates it).  backuwup never passes such sizes (dir_packer.rs:254-259); the
-    // ABI refuses them instead of returning chunks the crate would not.
-    if (av > mx) return BW_EINVAL;
-    const uint32_t bits = (uint32_t)lround(log2((double)av));  // logarithm2(): round(log2(avg))
-    mk->min = mn;
-    mk->avg = av;
-    mk->max = mx;
-    mk->s0 = 2 * (mn / 2);
-    mk->mask_s = H_MASKS[bits + 1];  // Normalization::Level1
-    mk->mask_l = H_MASKS[bits - 1];
-    mk->mask_pre = mk->mask_s & mk->mask_l;
-    mk->pre_shift = (uint32_t)__builtin_clzll(mk->mask_s | mk->mask_l);  // 63 - top bit
-    mk->pre_hi = (uint32_t)((mk->mask_pre << mk->pre_shift) >> 32);
-    mk->tile_shift = SCAN_TILE_SHIFT;
-    return BW_OK;
-}
-
-static uint64_t seg_len_for(const Masks& mk, bool small_batch) {
-    // Segments are a multiple of max_size so that chains through data without candidates
-    // (e.g. zeros: every chunk is exactly max) stay phase-aligned and merge immediately; the
-    // multiple keeps a segment's own cuts within CHAIN_CAP / 2.  Small batches take at most 2 x max:
-    // their chain walk is latency on the critical path (one wave walks a segment's cuts one after
-    // another, ~1.7 us each), and more, shorter segments walk in parallel.
-    uint64_t k = (uint64_t)(CHAIN_CAP / 2) * std::min<uint64_t>(mk.s0, mk.max) / mk.max;
-    if (k < 1) k = 1;
-    if (k > (small_batch ? 2 : 8)) k = small_batch ? 2 : 8;
-    return k * mk.max;
 }
 
 // ------------------------------------------------------------------ stage timing
@@ -699,26 +655,9 @@ Slot* slot_of(bw_ctx* c, uint64_t ticket) {
     return s->ticket == ticket ? s : nullptr;
 }
 
-static int validate_batch(bw_ctx* c, uint64_t data_len, const uint64_t* foff, const uint64_t* flen, uint64_t nf,
-                          const bw_params* prm, Masks* mk) {
-    if (int rc = make_masks(prm->min_size, prm->avg_size, prm->max_size, mk)) {
-        c->err = "fastcdc parameters out of range";
-        return rc;
-    }
-    if (nf && (!foff || !flen)) return BW_EINVAL;
-    for (uint64_t f = 0; f < nf; f++)
-        if (foff[f] > data_len || flen[f] > data_len - foff[f]) {
-            c->err = "file " + std::to_string(f) + " lies outside the data buffer";
-            return BW_EINVAL;
-        }
-    return BW_OK;
-}
-
-// Queue the host copies of a batch's results behind its kernels on the context stream: the
-// counters and the first res_n packed records (about twice the previous batch's blob count: a
-// guess, the rest is copied at the wait if the batch has more) into the slot's pinned buffer.
 // The results a bw_wait returns without touching the device: the counters and the first `want`
-// records in the slot's pinned buffer.  stage_prepare sizes the buffer (before the batch's last
+// records (about twice the previous batch's blob count: a guess, the rest is copied at the wait)
+// in the slot's pinned buffer.  stage_prepare sizes the buffer (before the batch's last
 // kernel, which may write it directly: `*zero_copy`); stage_results copies what that kernel did not
 // write and records `done`.
 constexpr uint64_t ZERO_COPY_MAX = 4ull << 20;  // larger result sets go by DMA copy
@@ -747,400 +686,267 @@ int stage_results(bw_ctx* c, Slot& s, bool written, uint64_t want, hipStream_t s
     return BW_OK;
 }
 
-// Enqueue one batch (bytes at d_data, in HBM) into slot `s` on the context stream.
-static int submit(bw_ctx* c, Slot& s, const uint8_t* d_data, uint64_t data_len, const uint64_t* foff,
-                  const uint64_t* flen, uint64_t nf, const bw_params* prm, bool stage = true, bool order_force = false) {
-    Masks mk;
-    if (int rc = validate_batch(c, data_len, foff, flen, nf, prm, &mk)) return rc;
-    if (data_len && !d_data) return BW_EINVAL;
-    if (((uintptr_t)d_data & 15) != 0) {
-        c->err = "device data pointer must be 16-byte aligned";
-        return BW_EINVAL;
-    }
-    hipSetDevice(c->device);
-    auto clk = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_mark = c->host_timing ? clk() : 0;
-    auto phase = [&](int k) {
-        if (!c->host_timing) return;
-        const double t = clk();
-        c->host_ms[k] += t - t_mark;
-        t_mark = t;
-    };
-    const bool force_serial = (prm->flags & BW_F_SERIAL_RESOLVE) != 0;
-    const bool do_hash = !(prm->flags & BW_F_NO_HASH);
-    const bool do_dedup = do_hash && !(prm->flags & BW_F_NO_DEDUP);
+// One batch's device views and launch geometry: what the enqueue groups below share.
+struct BatchViews {
+    const uint8_t* data;  // the batch bytes
+    uint64_t* ctr;        // the slot's counters
+    hipStream_t st, lat;  // the context stream; the latency stream (st unless BW_OPT_LATENCY_STREAM)
+    bool order;           // scans and leaf passes in submission order (BW_OPT_ORDER_HASH, split parts)
+    BlobArrays b;
+    uint64_t cand_cap, max_groups, want;  // want: records staged for the host (stage_prepare)
+    int max_leaves;
+    bool zero_copy;  // k_pack writes the staged records into the slot's pinned buffer itself
+};
 
-    // ---- the scan's tiles and buffers
-    // CDC files and the blob bound (the same bound as the tables below give): the result buffer
-    // holds the counters the scan writes, so it is sized before the scan is enqueued
-    uint64_t ncf_pre = 0, mb_pre = 0;
-    {
-        const uint64_t mc = std::min<uint64_t>(mk.s0, mk.max);
-        for (uint64_t f = 0; f < nf; f++) {
-            const bool cdc = flen[f] > prm->small_file_threshold && flen[f] > 0;
-            ncf_pre += cdc;
-            mb_pre += cdc ? flen[f] / mc + 2 : 1;
-        }
+// ---- device buffers.  scan_only: the scan's tiles, and the result buffer, which holds the
+// counters the scan writes, so it is sized before the scan is enqueued; the rest follows the tables
+static int reserve_buffers(bw_ctx* c, Slot& s, const BatchPlan& pl, BatchViews& v, bool scan_only) {
+    const uint64_t n_tiles = pl.n_tiles, nseg = pl.nseg, ncf = pl.ncf, max_blobs = pl.max_blobs;
+    int rc = 0;
+    if (scan_only) {
+        rc |= ensure(c, c->tile_count, n_tiles * 4);
+        rc |= ensure(c, c->tile_slots, n_tiles * SCAN_CAP * 8);
+        rc |= ensure(c, c->ovf, n_tiles * 4);
+        rc |= ensure(c, s.res_dev, CTR_BYTES + max_blobs * sizeof(bw_blob));
+        return rc ? BW_ENOMEM : BW_OK;
     }
-    // small batches scan half-size tiles: with one 128 KiB tile per wave the per-tile start
-    // costs dominate (C1: 0.50 -> 0.33 ms per GiB); large ones keep the longer strips
-    // (BW_OPT_SCAN_SMALL_BYTES moves the threshold, so the tests can run either tile size on any input)
-    mk.tile_shift = data_len < c->scan_small_bytes ? SCAN_TILE_SHIFT - 1 : SCAN_TILE_SHIFT;
-    const uint64_t tile_bytes = 1ull << mk.tile_shift;
-    const uint64_t n_tiles = ncf_pre ? (data_len + tile_bytes - 1) / tile_bytes : 0;
-    {
-        int rc0 = 0;
-        rc0 |= ensure(c, c->tile_count, n_tiles * 4);
-        rc0 |= ensure(c, c->tile_slots, n_tiles * SCAN_CAP * 8);
-        rc0 |= ensure(c, c->ovf, n_tiles * 4);
-        rc0 |= ensure(c, s.res_dev, CTR_BYTES + mb_pre * sizeof(bw_blob));
-        if (rc0) return BW_ENOMEM;
-    }
-    // ---- the gear scan: counters zeroed, then the scan; it reads only the batch bytes and the
-    // tile buffers above
-    auto enqueue_scan = [&]() -> int {
-        // (a kernel of ours: after hipMemsetAsync's fill the scan started ~5.4 us later)
-        launch_zero(c->stream, slot_ctr(s), C_COUNT);
-        if (c->prof) {
-            c->ev_set ^= 1;
-            prof_collect(c, c->ev_set);  // the set about to be reused belongs to batch k-2
-        }
-        prof_mark(c, BW_STAGE_SCAN);
-        if (!ncf_pre) return BW_OK;
-        bw_index* x = c->idx;
-        std::unique_lock<std::mutex> lk(x->mu, std::defer_lock);
-        if (c->order_hash || order_force) {
-            lk.lock();
-            if (x->scan_tail_set) HIPCHK(c, hipStreamWaitEvent(c->stream, x->scan_tail, 0));
-        }
-        if (!launch_scan(c->stream, d_data, data_len, n_tiles, mk, P<uint32_t>(c->tile_count),
-                         P<uint64_t>(c->tile_slots), P<uint32_t>(c->ovf), slot_ctr(s), c->scan_waves)) {
-            c->err = "no scan kernel for tile size 2^" + std::to_string(mk.tile_shift);
-            return BW_EINVAL;
-        }
-        if (c->order_hash || order_force) {
-            HIPCHK(c, hipEventRecord(x->scan_tail, c->stream));
-            x->scan_tail_set = true;
-        }
-        return BW_OK;
-    };
-    // Small batches enqueue it before the host tables, so the GPU starts while the host builds
-    // them (one batch in flight: the host's share of a 1 GiB batch sits on the critical path).
-    // Large ones keep it behind the upload: enqueued first, it made C3's two contexts fall into a
-    // slower phase in one run of two (1,647 vs 1,871 GB/s; profiles/r02/s31_reorder).
-    const bool scan_first = c->scan_first == 2 ? data_len < c->scan_small_bytes : c->scan_first == 1;
-    if (scan_first)
-        if (int r6 = enqueue_scan()) return r6;
-
-    // ---- host metadata: CDC files, segments, canonical units
-    const uint64_t L = seg_len_for(mk, data_len < c->scan_small_bytes);
-    // every chunk but a file's last is >= min(2*(min/2), max) bytes (max < min is legal in the crate)
-    const uint64_t min_chunk = std::min<uint64_t>(mk.s0, mk.max);
-    // Two passes over file ranges (in parallel for large batches: C4's million files took ~4 ms on
-    // one thread): count each range's segments, CDC files, units and bounds, then fill the tables
-    // at the ranges' prefix offsets.  The tables are the same as one serial walk in file order.
-    struct Part {
-        uint64_t nseg = 0, ncf = 0, nunits = 0, fb = 0, max_blobs = 0, total_len = 0, max_blob_len = 0;
-    };
-    const uint64_t T = nf >= 65536 ? 64 : 1;
-    std::vector<Part> part(T), base(T);
-    auto is_cdc = [&](uint64_t f) { return flen[f] > prm->small_file_threshold && flen[f] > 0; };
-    parallel_ranges(T, [&](uint64_t k0, uint64_t k1) {
-        for (uint64_t k = k0; k < k1; k++) {
-            Part& q = part[k];
-            for (uint64_t f = nf * k / T; f < nf * (k + 1) / T; f++) {
-                q.total_len += flen[f];
-                if (is_cdc(f)) {
-                    const uint64_t ns = (flen[f] + L - 1) / L, nb = flen[f] / min_chunk + 2;
-                    q.nseg += ns;
-                    q.nunits += ns;
-                    q.ncf++;
-                    q.fb += nb;
-                    q.max_blobs += nb;
-                } else {
-                    q.nunits++;
-                    q.max_blobs++;
-                    q.max_blob_len = std::max<uint64_t>(q.max_blob_len, flen[f]);
-                }
-            }
-        }
-    }, nf);
-    Part tot;
-    // a CDC chunk is <= max, or <= min where cut() returns a remainder <= min whole before clipping
-    // to max (min > max is legal in the crate; round-6 fuzz: a 70,325 B chunk under max = 1,520)
-    tot.max_blob_len = std::max<uint64_t>(mk.max, mk.min);
-    for (uint64_t k = 0; k < T; k++) {
-        base[k] = tot;
-        tot.nseg += part[k].nseg;
-        tot.ncf += part[k].ncf;
-        tot.nunits += part[k].nunits;
-        tot.fb += part[k].fb;
-        tot.max_blobs += part[k].max_blobs;
-        tot.total_len += part[k].total_len;
-        tot.max_blob_len = std::max(tot.max_blob_len, part[k].max_blob_len);
-    }
-    // the tables are written straight into the slot's pinned staging, from which they are uploaded
-    // (a million files' 40 MB of tables were a vector build plus one serial memcpy before)
-    const uint64_t nseg = tot.nseg, ncf = tot.ncf, nunits = tot.nunits;
-    const size_t meta_bytes = nseg * sizeof(SegDesc) + ncf * sizeof(CFileDesc) + nunits * sizeof(UnitDesc) + nf * 8;
-    if (s.meta_pending) {
-        hipEventSynchronize(s.meta_on_done ? s.done : s.meta_done);
-        s.meta_pending = false;
-    }
-    if (int r3 = ensure_host(c, s.meta, meta_bytes + 64)) return r3;
-    SegDesc* segs = (SegDesc*)s.meta.p;
-    CFileDesc* cfs = (CFileDesc*)(segs + nseg);
-    UnitDesc* units = (UnitDesc*)(cfs + ncf);
-    uint64_t* fstart_h = (uint64_t*)(units + nunits);
-    static_assert(sizeof(SegDesc) % 8 == 0 && sizeof(CFileDesc) % 8 == 0 && sizeof(UnitDesc) % 8 == 0, "staging alignment");
-    parallel_ranges(T, [&](uint64_t k0, uint64_t k1) {
-        for (uint64_t k = k0; k < k1; k++) {
-            uint64_t si = base[k].nseg, ci = base[k].ncf, ui = base[k].nunits, fb = base[k].fb;
-            const uint64_t f0 = nf * k / T, f1 = nf * (k + 1) / T;
-            if (f1 > f0) memcpy(fstart_h + f0, foff + f0, (f1 - f0) * 8);
-            for (uint64_t f = f0; f < f1; f++) {
-                if (is_cdc(f)) {
-                    CFileDesc cf;
-                    cf.start = foff[f];
-                    cf.end = foff[f] + flen[f];
-                    cf.fb_off = fb;
-                    cf.first_seg = (uint32_t)si;
-                    const uint64_t ns = (flen[f] + L - 1) / L;
-                    cf.nseg = (uint32_t)ns;
-                    for (uint64_t j = 0; j < ns; j++) {
-                        SegDesc sd;
-                        sd.start = cf.start + j * L;
-                        sd.end = std::min(cf.start + (j + 1) * L, cf.end);
-                        sd.file_end = cf.end;
-                        sd.cfile = (uint32_t)ci;
-                        sd.last = j + 1 == ns;
-                        UnitDesc u;
-                        u.start = 0;
-                        u.len = 0;
-                        u.file = (uint32_t)f;
-                        u.kind = 1;
-                        u.seg = (uint32_t)si;
-                        u.cfile = sd.cfile;
-                        units[ui++] = u;
-                        segs[si++] = sd;
-                    }
-                    fb += flen[f] / min_chunk + 2;
-                    cfs[ci++] = cf;
-                } else {
-                    UnitDesc u;
-                    u.start = foff[f];
-                    u.len = flen[f];
-                    u.file = (uint32_t)f;
-                    u.kind = 0;
-                    u.seg = 0;
-                    u.cfile = 0;
-                    units[ui++] = u;
-                }
-            }
-        }
-    }, nf);
-    const uint64_t max_blobs = tot.max_blobs, fb_total = tot.fb, max_blob_len = tot.max_blob_len,
-                   total_len = tot.total_len;
     // Leaves per BLAKE3 group (one lane each) of the aligned-line leaf pass.  Auto: 2 for small
     // batches (under BW_OPT_SCAN_SMALL_BYTES: the pass's last partial round of waves is a large share
     // of it) and for batches of small blobs (mean blob bound under 128 KiB: fewer lanes idle in a
     // blob's ragged last group); 4 otherwise (the upper levels' extra work is not paid back).
     // Measured (profiles/r03/s05_group): C1 one batch in flight +3 %, C1 three +1.7 %, C4 +9.5 %,
     // C2 -1.3 % with 2.
-    const bool small_groups = data_len < c->scan_small_bytes || total_len < max_blobs * (128ull << 10);
+    const bool small_groups = pl.data_len < c->scan_small_bytes || pl.total_len < max_blobs * (128ull << 10);
     const int grp = c->b3_group ? c->b3_group : (small_groups ? 2 : 4);
     const uint32_t gshift = c->b3_loads != B3_LOADS_LINES ? 2 : (grp == 1 ? 0 : grp == 2 ? 1 : 2);
-    const uint64_t max_groups = total_len / (1024ull << gshift) + max_blobs + 1;  // 1 KiB BLAKE3 leaves
-    const int max_leaves = (int)std::min<uint64_t>((max_blob_len + 1023) / 1024, 1u << 30);
-    if (ncf != ncf_pre || max_blobs != mb_pre) return BW_ESTATE;  // the same sums as the pre-count; cannot differ
-
-    // ---- device buffers
-    phase(0);
-    int rc = 0;
-    rc |= ensure(c, c->tile_off, (n_tiles + 1) * 8);
-    rc |= ensure(c, c->tile_btot, (n_tiles / 1024 + 2) * 8);
-    rc |= ensure(c, c->meta, meta_bytes);  // segs | cfiles | units | fstart, as staged
-    rc |= ensure(c, c->chains, nseg * CHAIN_CAP * 8);
-    rc |= ensure(c, c->chain_n, nseg * 4);
-    rc |= ensure(c, c->chain_cptr, nseg * 8);
-    rc |= ensure(c, c->merge, nseg * 8);
-    rc |= ensure(c, c->seg_M, nseg * 8);
-    rc |= ensure(c, c->seg_cnt, nseg * 4);
-    rc |= ensure(c, c->cf_invalid, ncf * 4);
-    rc |= ensure(c, c->fb_starts, fb_total * 8);
-    rc |= ensure(c, c->fb_count, ncf * 8);
-    rc |= ensure(c, c->b_start, max_blobs * 8);
-    rc |= ensure(c, c->b_len, max_blobs * 8);
-    rc |= ensure(c, c->b_goff, max_blobs * 8);
-    rc |= ensure(c, c->b_file, max_blobs * 4);
-    rc |= ensure(c, c->b_kind, max_blobs * 4);
-    rc |= ensure(c, c->b_fend, max_blobs * 8);
-    rc |= ensure(c, c->b_ghash, max_blobs * 8);
-    if (c->b_gdone.cap < max_blobs * 4) {  // the passes leave it zeroed; a new buffer starts so
-        rc |= ensure(c, c->b_gdone, max_blobs * 4);
-        if (!rc) HIPCHK(c, hipMemsetAsync(c->b_gdone.p, 0, c->b_gdone.cap, c->stream));
-    }
-    rc |= ensure(c, c->cv, max_groups * 32);
-    rc |= ensure(c, c->cv2, max_leaves > 64 ? max_groups * 32 : 16);
-    rc |= ensure(c, s.digests, max_blobs * 32);
-    rc |= ensure(c, s.is_dup, max_blobs);
-    rc |= ensure(c, c->ucnt, 2 * nunits * 8);
-    rc |= ensure(c, c->ubtot, 2 * (nunits / 256 + 2) * 8);
-    if (rc) return BW_ENOMEM;
+    v.max_groups = pl.total_len / (1024ull << gshift) + max_blobs + 1;  // 1 KiB BLAKE3 leaves
+    v.max_leaves = (int)std::min<uint64_t>((pl.max_blob_len + 1023) / 1024, 1u << 30);
     // candidate array: 4x the expected count (2^-popcount(mask) per byte) plus slack.  A batch that
     // finds more stays exact (the walkers test the bytes past the array's end, C_TRUNC) and the
     // next batch gets the room it would have needed.
-    uint64_t cand_cap = 16;
+    v.cand_cap = 16;
     if (ncf) {
-        const int bits = __builtin_popcountll(mk.mask_pre);
-        cand_cap = 4 * (data_len >> bits) + 2 * n_tiles + 4096;
-        cand_cap = std::max(cand_cap, c->cand_override);
-        if (c->cand_cap_forced) cand_cap = c->cand_cap_forced;
+        const int bits = __builtin_popcountll(pl.mk.mask_pre);
+        v.cand_cap = 4 * (pl.data_len >> bits) + 2 * n_tiles + 4096;
+        v.cand_cap = std::max(v.cand_cap, c->cand_override);
+        if (c->cand_cap_forced) v.cand_cap = c->cand_cap_forced;
     }
-    if (int r2 = ensure(c, c->cand, cand_cap * 8)) return r2;
-
-    // ---- metadata upload through the slot's pinned staging
-    phase(1);
-    auto up = [&](DevBuf& dst, const void* src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(dst.p, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+    const struct { DevBuf& b; uint64_t bytes; } need[] = {
+        {c->tile_off, (n_tiles + 1) * 8}, {c->tile_btot, (n_tiles / 1024 + 2) * 8},
+        {c->meta, pl.meta_bytes},  // segs | cfiles | units | fstart, as staged
+        {c->chains, nseg * CHAIN_CAP * 8}, {c->chain_n, nseg * 4}, {c->chain_cptr, nseg * 8}, {c->merge, nseg * 8},
+        {c->seg_M, nseg * 8}, {c->seg_cnt, nseg * 4},
+        {c->cf_invalid, ncf * 4}, {c->fb_starts, pl.fb_total * 8}, {c->fb_count, ncf * 8},
+        {c->b_start, max_blobs * 8}, {c->b_len, max_blobs * 8}, {c->b_goff, max_blobs * 8}, {c->b_file, max_blobs * 4},
+        {c->b_kind, max_blobs * 4}, {c->b_fend, max_blobs * 8}, {c->b_ghash, max_blobs * 8}, {c->b_gdone, max_blobs * 4},
+        {c->cv, v.max_groups * 32}, {c->cv2, v.max_leaves > 64 ? v.max_groups * 32 : 16},
+        {s.digests, max_blobs * 32}, {s.is_dup, max_blobs},
+        {c->ucnt, 2 * pl.nunits * 8}, {c->ubtot, 2 * (pl.nunits / 256 + 2) * 8}, {c->cand, v.cand_cap * 8},
     };
+    for (const auto& n : need) {
+        if (&n.b != &c->b_gdone) rc |= ensure(c, n.b, n.bytes);
+        else if (n.b.cap < n.bytes) {  // the passes leave it zeroed; a new buffer starts so
+            rc |= ensure(c, n.b, n.bytes);
+            if (!rc) HIPCHK(c, hipMemsetAsync(n.b.p, 0, n.b.cap, c->stream));
+        }
+    }
+    if (rc) return BW_ENOMEM;
+    v.b = BlobArrays{P<uint64_t>(c->b_start), P<uint64_t>(c->b_len), P<uint64_t>(c->b_goff), P<uint32_t>(c->b_file),
+                     P<uint32_t>(c->b_kind), P<uint64_t>(c->b_fend), P<uint64_t>(c->b_ghash), max_blobs, pl.data_len,
+                     c->b3_fused ? P<uint32_t>(c->b_gdone) : nullptr, gshift};
+    return BW_OK;
+}
+
+// ---- the gear scan: counters zeroed, then the scan; it reads only the batch bytes and the
+// tile buffers above
+static int enqueue_scan(bw_ctx* c, const BatchPlan& pl, const BatchViews& v) {
+    // (a kernel of ours: after hipMemsetAsync's fill the scan started ~5.4 us later)
+    launch_zero(v.st, v.ctr, C_COUNT);
+    if (c->prof) {
+        c->ev_set ^= 1;
+        prof_collect(c, c->ev_set);  // the set about to be reused belongs to batch k-2
+    }
+    prof_mark(c, BW_STAGE_SCAN);
+    if (!pl.ncf) return BW_OK;
+    bw_index* x = c->idx;
+    std::unique_lock<std::mutex> lk(x->mu, std::defer_lock);
+    if (v.order) {
+        lk.lock();
+        if (x->scan_tail_set) HIPCHK(c, hipStreamWaitEvent(v.st, x->scan_tail, 0));
+    }
+    if (!launch_scan(v.st, v.data, pl.data_len, pl.n_tiles, pl.mk, P<uint32_t>(c->tile_count),
+                     P<uint64_t>(c->tile_slots), P<uint32_t>(c->ovf), v.ctr, c->scan_waves)) {
+        c->err = "no scan kernel for tile size 2^" + std::to_string(pl.mk.tile_shift);
+        return BW_EINVAL;
+    }
+    if (v.order) {
+        HIPCHK(c, hipEventRecord(x->scan_tail, v.st));
+        x->scan_tail_set = true;
+    }
+    return BW_OK;
+}
+
+// `to` goes on after what `from` holds so far (the hops between the context and the latency stream)
+static int stream_hop(bw_ctx* c, hipEvent_t ev, hipStream_t from, hipStream_t to) {
+    HIPCHK(c, hipEventRecord(ev, from));
+    HIPCHK(c, hipStreamWaitEvent(to, ev, 0));
+    return BW_OK;
+}
+
+// ---- metadata upload through the slot's pinned staging
+static int upload_tables(bw_ctx* c, Slot& s, const BatchPlan& pl, bool stage) {
     // one copy: the tables lie back to back in the staging and keep that layout on the device.
     // Up to 1 MiB a kernel reads them over PCIe (no copy-engine round trip on the stream); more
     // (C4's million units, ~40 MB) go by DMA.
-    if (meta_bytes <= (1u << 20)) launch_upload(c->stream, segs, c->meta.p, meta_bytes);
-    else HIPCHK(c, up(c->meta, segs, meta_bytes));
-    SegDesc* d_segs = P<SegDesc>(c->meta);
-    CFileDesc* d_cfs = (CFileDesc*)(d_segs + nseg);
-    UnitDesc* d_units = (UnitDesc*)(d_cfs + ncf);
-    uint64_t* d_fstart = (uint64_t*)(d_units + nunits);
+    if (pl.meta_bytes <= (1u << 20)) launch_upload(c->stream, s.meta.p, c->meta.p, pl.meta_bytes);
+    else HIPCHK(c, hipMemcpyAsync(c->meta.p, s.meta.p, pl.meta_bytes, hipMemcpyHostToDevice, c->stream));
     // The staging is refilled when the slot comes round again, `depth` batches later: for a staged
     // batch of a context that keeps two or more, the batch's own end (`done`) covers the upload, so
     // no event goes between the upload and the next kernel (each costs the stream ~5.5 us)
     s.meta_on_done = stage && c->depth >= 2;
     if (!s.meta_on_done) HIPCHK(c, hipEventRecord(s.meta_done, c->stream));
     s.meta_pending = true;
-    phase(2);
+    return BW_OK;
+}
 
-    if (!scan_first)
-        if (int r6 = enqueue_scan()) return r6;
-    uint64_t* ctr = slot_ctr(s);
-    hipStream_t st = c->stream;
-
-    BlobArrays b{P<uint64_t>(c->b_start), P<uint64_t>(c->b_len), P<uint64_t>(c->b_goff), P<uint32_t>(c->b_file),
-                 P<uint32_t>(c->b_kind), P<uint64_t>(c->b_fend), P<uint64_t>(c->b_ghash), max_blobs, data_len,
-                 c->b3_fused ? P<uint32_t>(c->b_gdone) : nullptr, gshift};
-
-    // ---- chunking (the scan on the context stream, the latency-bound kernels after it on `lat`)
-    const bool split = c->lat_split;
-    hipStream_t lat = split ? c->hi : st;
-    if (split) {
-        HIPCHK(c, hipEventRecord(c->e_scan, st));
-        HIPCHK(c, hipStreamWaitEvent(lat, c->e_scan, 0));
-    }
-    prof_mark(c, BW_STAGE_COMPACT, lat);
+// ---- chunking (the scan on the context stream, the latency-bound kernels after it on `lat`), then
+// hashing (the leaf pass on the context stream, the upper levels on lat)
+static int enqueue_chunk_hash(bw_ctx* c, Slot& s, const BatchPlan& pl, const BatchViews& v, bool force_serial, bool do_hash) {
+    const uint64_t nseg = pl.nseg, ncf = pl.ncf;
+    uint64_t* cand = P<uint64_t>(c->cand), *tile_off = P<uint64_t>(c->tile_off), *chains = P<uint64_t>(c->chains);
+    const SegDesc* segs = pl.segs(c->meta.p);
+    const CFileDesc* cfs = pl.cfiles(c->meta.p);
+    if (c->lat_split && stream_hop(c, c->e_scan, v.st, v.lat)) return BW_EHIP;
+    prof_mark(c, BW_STAGE_COMPACT, v.lat);
     if (ncf)
-        launch_compact(lat, d_data, data_len, n_tiles, mk, P<uint32_t>(c->tile_count), P<uint64_t>(c->tile_slots),
-                       P<uint64_t>(c->tile_off), P<uint64_t>(c->cand), cand_cap, P<uint32_t>(c->ovf), ctr,
+        launch_compact(v.lat, v.data, pl.data_len, pl.n_tiles, pl.mk, P<uint32_t>(c->tile_count),
+                       P<uint64_t>(c->tile_slots), tile_off, cand, v.cand_cap, P<uint32_t>(c->ovf), v.ctr,
                        P<uint64_t>(c->tile_btot));
-    prof_mark(c, BW_STAGE_RESOLVE, lat);
+    prof_mark(c, BW_STAGE_RESOLVE, v.lat);
     if (ncf) {
-        launch_chains(lat, d_data, data_len, mk, P<uint64_t>(c->cand), P<uint64_t>(c->tile_off), ctr, d_segs,
-                      nseg, P<uint64_t>(c->chains), P<uint32_t>(c->chain_n), P<uint64_t>(c->chain_cptr),
-                      P<uint64_t>(c->merge), force_serial);
-        launch_resolve(lat, d_data, data_len, mk, P<uint64_t>(c->cand), P<uint64_t>(c->tile_off), ctr,
-                       d_segs, nseg, d_cfs, ncf, P<uint64_t>(c->chains),
+        launch_chains(v.lat, v.data, pl.data_len, pl.mk, cand, tile_off, v.ctr, segs, nseg, chains,
+                      P<uint32_t>(c->chain_n), P<uint64_t>(c->chain_cptr), P<uint64_t>(c->merge), force_serial);
+        launch_resolve(v.lat, v.data, pl.data_len, pl.mk, cand, tile_off, v.ctr, segs, nseg, cfs, ncf, chains,
                        P<uint32_t>(c->chain_n), P<uint64_t>(c->merge), P<uint64_t>(c->seg_M), P<uint32_t>(c->seg_cnt),
                        P<uint32_t>(c->cf_invalid), P<uint64_t>(c->fb_starts), P<uint64_t>(c->fb_count), force_serial);
     }
-    prof_mark(c, BW_STAGE_ASSEMBLE, lat);
-    launch_assemble(lat, ctr, d_units, nunits, d_segs, d_cfs,
-                    P<uint64_t>(c->chains), P<uint32_t>(c->chain_n), P<uint64_t>(c->seg_M), P<uint32_t>(c->cf_invalid),
-                    P<uint64_t>(c->fb_starts), P<uint64_t>(c->fb_count), b, P<uint64_t>(c->ucnt),
-                    P<uint64_t>(c->ubtot));
+    prof_mark(c, BW_STAGE_ASSEMBLE, v.lat);
+    launch_assemble(v.lat, v.ctr, pl.units(c->meta.p), pl.nunits, segs, cfs, chains, P<uint32_t>(c->chain_n),
+                    P<uint64_t>(c->seg_M), P<uint32_t>(c->cf_invalid), P<uint64_t>(c->fb_starts),
+                    P<uint64_t>(c->fb_count), v.b, P<uint64_t>(c->ucnt), P<uint64_t>(c->ubtot));
     // Chunk.hash: one wave per chunk (a thread-serial version inside k_unit_emit made C1's
     // assembly 0.03 -> 0.31 ms: 64 dependent byte loads per chunk)
-    if (ncf) launch_cut_hash(lat, d_data, mk, ctr, b, max_blobs);
-    else HIPCHK(c, hipMemsetAsync(c->b_ghash.p, 0, max_blobs * 8, lat));
-    if (split) {
-        HIPCHK(c, hipEventRecord(c->e_lat, lat));
-        HIPCHK(c, hipStreamWaitEvent(st, c->e_lat, 0));
-    }
-
-    // ---- hashing (the leaf pass on the context stream, the upper levels on lat) + dedup on lat
-    prof_mark(c, BW_STAGE_B3LEAF, st);
+    if (ncf) launch_cut_hash(v.lat, v.data, pl.mk, v.ctr, v.b, pl.max_blobs);
+    else HIPCHK(c, hipMemsetAsync(c->b_ghash.p, 0, pl.max_blobs * 8, v.lat));
+    if (c->lat_split && stream_hop(c, c->e_lat, v.lat, v.st)) return BW_EHIP;
+    prof_mark(c, BW_STAGE_B3LEAF, v.st);
     if (do_hash) {
         // the B3TREE stage mark (timing only) and the event that orders the upper levels' stream
         // after the leaf pass (split latency stream) are separate events
         hipEvent_t mark = c->prof && ((c->prof_mask >> BW_STAGE_B3TREE) & 1) ? c->ev[c->ev_set][BW_STAGE_B3TREE] : nullptr;
-        hipEvent_t between = split ? c->e_b3 : nullptr;
+        hipEvent_t between = c->lat_split ? c->e_b3 : nullptr;
         bw_index* x = c->idx;
         std::unique_lock<std::mutex> lk(x->mu, std::defer_lock);
-        const bool order = c->order_hash || order_force;
-        if (order) {
+        if (v.order) {
             lk.lock();
-            if (x->hash_tail_set) HIPCHK(c, hipStreamWaitEvent(st, x->hash_tail, 0));
+            if (x->hash_tail_set) HIPCHK(c, hipStreamWaitEvent(v.st, x->hash_tail, 0));
         }
-        launch_blake3(st, d_data, ctr, b, max_blobs, max_groups, P<uint32_t>(c->cv), P<uint32_t>(c->cv2),
-                      P<uint8_t>(s.digests), max_leaves, between, c->b3_loads, lat, order ? x->hash_tail : nullptr, mark);
-        if (order) x->hash_tail_set = true;
+        launch_blake3(v.st, v.data, v.ctr, v.b, pl.max_blobs, v.max_groups, P<uint32_t>(c->cv), P<uint32_t>(c->cv2),
+                      P<uint8_t>(s.digests), v.max_leaves, between, c->b3_loads, v.lat, v.order ? x->hash_tail : nullptr,
+                      mark);
+        if (v.order) x->hash_tail_set = true;
     } else {
-        prof_mark(c, BW_STAGE_B3TREE, st);
-        if (split) {
-            HIPCHK(c, hipEventRecord(c->e_b3, st));
-            HIPCHK(c, hipStreamWaitEvent(lat, c->e_b3, 0));
-        }
-        HIPCHK(c, hipMemsetAsync(s.digests.p, 0, max_blobs * 32, lat));
+        prof_mark(c, BW_STAGE_B3TREE, v.st);
+        if (c->lat_split && stream_hop(c, c->e_b3, v.st, v.lat)) return BW_EHIP;
+        HIPCHK(c, hipMemsetAsync(s.digests.p, 0, pl.max_blobs * 32, v.lat));
     }
     // no kernel of this batch reads d_data after here; only the slot's own input buffer (host
     // batches, stream_in) is ever refilled behind this event
-    if (d_data == P<uint8_t>(s.input)) HIPCHK(c, hipEventRecord(s.input_free, st));
-    phase(3);
-    prof_mark(c, BW_STAGE_DEDUP, lat);
+    if (v.data == P<uint8_t>(s.input)) HIPCHK(c, hipEventRecord(s.input_free, v.st));
+    return BW_OK;
+}
+
+// ---- the gate (dedup on lat) and the pack
+static int enqueue_gate_pack(bw_ctx* c, Slot& s, const BatchPlan& pl, BatchViews& v, bool do_dedup, bool stage) {
+    prof_mark(c, BW_STAGE_DEDUP, v.lat);
     // small result sets are written to the slot's pinned buffer by k_pack itself (no copy on the
     // stream: pack -> copy cost a 12 us gap with one batch in flight, profiles/r03/s07_upper_block)
-    uint64_t want = 0;
-    bool zero_copy = false;
     if (stage)
-        if (int r5 = stage_prepare(c, s, max_blobs, &want, &zero_copy)) return r5;
-    auto pack = [&](hipStream_t ps) {
+        if (int rc = stage_prepare(c, s, v.b.cap, &v.want, &v.zero_copy)) return rc;
+    auto pack = [&](hipStream_t ps) {  // (a gated batch's: inside the index operation, before its tail event)
         prof_mark(c, BW_STAGE_PACK, ps);
-        launch_pack(ps, ctr, b, d_fstart, P<uint8_t>(s.digests), do_dedup ? P<uint8_t>(s.is_dup) : nullptr,
-                    slot_records(s), max_blobs, do_dedup ? P<uint64_t>(c->idx->dstate) : nullptr,
-                    zero_copy ? (uint8_t*)s.res.p : nullptr, want);
+        launch_pack(ps, v.ctr, v.b, pl.fstart(c->meta.p), P<uint8_t>(s.digests),
+                    do_dedup ? P<uint8_t>(s.is_dup) : nullptr, slot_records(s), v.b.cap,
+                    do_dedup ? P<uint64_t>(c->idx->dstate) : nullptr, v.zero_copy ? (uint8_t*)s.res.p : nullptr, v.want);
     };
-    if (do_dedup) {  // the pack runs inside the index operation (before its tail event)
-        if (int r4 = dedup_device(c, P<uint8_t>(s.digests), ctr + C_DEDUPN, 0, max_blobs, P<uint8_t>(s.is_dup), lat,
-                                  pack))
-            return r4;
-        s.mark = c->idx_mark;
-    } else {
-        pack(lat);
+    if (!do_dedup) pack(v.lat);
+    else if (int rc = dedup_device(c, P<uint8_t>(s.digests), v.ctr + C_DEDUPN, 0, v.b.cap, P<uint8_t>(s.is_dup), v.lat, pack))
+        return rc;
+    else s.mark = c->idx_mark;
+    return BW_OK;
+}
+
+// closes phase k of submit's host-side time (bw_ctx::host_ms); k < 0 starts the clock
+static void phase(bw_ctx* c, double& t, int k) {
+    if (!c->host_timing) return;
+    const double n = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    if (k >= 0) c->host_ms[k] += n - t;
+    t = n;
+}
+
+// Enqueue one batch (bytes at d_data, in HBM; pl: its checked file list) into slot `s` on the context stream:
+// count -> [scan] -> tables -> buffers -> upload -> [scan] -> chunking -> hashing -> gate and pack -> staged results.
+static int submit(bw_ctx* c, Slot& s, const uint8_t* d_data, BatchPlan& pl, bool stage = true, bool order_force = false) {
+    if (pl.data_len && !d_data) return BW_EINVAL;
+    if (((uintptr_t)d_data & 15) != 0) {
+        c->err = "device data pointer must be 16-byte aligned";
+        return BW_EINVAL;
     }
-    phase(4);
-    if (split) {  // the batch ends on the context stream (the caller's order)
-        prof_mark(c, BW_N_STAGES, lat);
-        HIPCHK(c, hipEventRecord(c->e_end, lat));
-        HIPCHK(c, hipStreamWaitEvent(st, c->e_end, 0));
-    }
-    if (!split) prof_mark(c, BW_N_STAGES);
+    hipSetDevice(c->device);
+    double t = 0;
+    phase(c, t, -1);
+    const bool do_hash = !(pl.prm->flags & BW_F_NO_HASH);
+    const bool do_dedup = do_hash && !(pl.prm->flags & BW_F_NO_DEDUP);
+    pl.count(c->scan_small_bytes);
+    BatchViews v{};
+    int rc = reserve_buffers(c, s, pl, v, true);
+    if (rc) return rc;
+    v.data = d_data, v.ctr = slot_ctr(s), v.st = c->stream, v.lat = c->lat_split ? c->hi : c->stream;
+    v.order = c->order_hash || order_force;
+    // Small batches enqueue the scan before the host tables, so the GPU starts while the host builds
+    // them (one batch in flight: the host's share of a 1 GiB batch sits on the critical path).
+    // Large ones keep it behind the upload: enqueued first, it made C3's two contexts fall into a
+    // slower phase in one run of two (1,647 vs 1,871 GB/s; profiles/r02/s31_reorder).
+    const bool scan_first = c->scan_first == 2 ? pl.data_len < c->scan_small_bytes : c->scan_first == 1;
+    if (scan_first && (rc = enqueue_scan(c, pl, v))) return rc;
+    // ---- host metadata: CDC files, segments, canonical units.  The tables are written straight into
+    // the slot's pinned staging, from which they are uploaded (a million files' 40 MB of tables were a
+    // vector build plus one serial memcpy before)
+    if (s.meta_pending) hipEventSynchronize(s.meta_on_done ? s.done : s.meta_done);
+    s.meta_pending = false;
+    if ((rc = ensure_host(c, s.meta, pl.meta_bytes + 64))) return rc;
+    pl.fill(s.meta.p);
+    phase(c, t, 0);
+    if ((rc = reserve_buffers(c, s, pl, v, false))) return rc;
+    phase(c, t, 1);
+    if ((rc = upload_tables(c, s, pl, stage))) return rc;
+    phase(c, t, 2);
+    if (!scan_first && (rc = enqueue_scan(c, pl, v))) return rc;
+    if ((rc = enqueue_chunk_hash(c, s, pl, v, (pl.prm->flags & BW_F_SERIAL_RESOLVE) != 0, do_hash))) return rc;
+    phase(c, t, 3);
+    if ((rc = enqueue_gate_pack(c, s, pl, v, do_dedup, stage))) return rc;
+    phase(c, t, 4);
+    prof_mark(c, BW_N_STAGES, v.lat);
+    // the batch ends on the context stream (the caller's order)
+    if (c->lat_split && stream_hop(c, c->e_end, v.lat, v.st)) return BW_EHIP;
     if (c->prof) c->ev_pending[c->ev_set] = true;
     HIPCHK(c, hipGetLastError());
-    s.max_blobs = max_blobs;
-    s.geo_tiles = n_tiles;
-    s.geo_cfiles = ncf;
-    s.geo_segs = nseg;
-    s.geo_tile_bytes = tile_bytes;
-    s.geo_seg_bytes = L;
-    s.dedup = do_dedup;
-    s.hashed = do_hash;
-    s.comm = nullptr;
-    s.ex_state = 0;
-    s.ex_rc = 0;
-    s.ex_first = 0;
-    s.ex_n = ~0ull;
-    if (stage)
-        if (int r5 = stage_results(c, s, zero_copy, want)) return r5;
-    phase(5);
+    s.max_blobs = pl.max_blobs, s.dedup = do_dedup, s.hashed = do_hash;
+    s.geo_tiles = pl.n_tiles, s.geo_cfiles = pl.ncf, s.geo_segs = pl.nseg;
+    s.geo_tile_bytes = pl.tile_bytes, s.geo_seg_bytes = pl.seg_bytes;
+    s.comm = nullptr, s.ex_state = 0, s.ex_rc = 0, s.ex_first = 0, s.ex_n = ~0ull;  // no exchange yet
+    if (stage && (rc = stage_results(c, s, v.zero_copy, v.want))) return rc;
+    phase(c, t, 5);
     c->host_batches += c->host_timing;
     return BW_OK;
 }
@@ -1200,9 +1006,10 @@ static int ensure_helper(bw_ctx* c) {
 // index (a NO_DEDUP batch's device views feed the multi-GPU exchange whole), hold at least two
 // files, and are large enough to amortise the second submission but small enough that one batch
 // in flight leaves the scan and BLAKE3 passes apart (large batches fill the chip either way).
-static uint64_t split_point(bw_ctx* c, uint64_t data_len, const uint64_t* flen, uint64_t nf, const bw_params* prm) {
-    if (c->split < 2 || c->is_helper || nf < 2 || (prm->flags & (BW_F_NO_DEDUP | BW_F_NO_HASH))) return 0;
-    if (data_len > c->split_max) return 0;
+static uint64_t split_point(bw_ctx* c, const BatchPlan& pl) {
+    const uint64_t nf = pl.nf, *flen = pl.flen;
+    if (c->split < 2 || c->is_helper || nf < 2 || (pl.prm->flags & (BW_F_NO_DEDUP | BW_F_NO_HASH))) return 0;
+    if (pl.data_len > c->split_max) return 0;
     uint64_t total = 0;
     for (uint64_t f = 0; f < nf; f++) total += flen[f];
     if (total < c->split_min) return 0;
@@ -1216,21 +1023,19 @@ static uint64_t split_point(bw_ctx* c, uint64_t data_len, const uint64_t* flen, 
 
 // Submit into slot s of c, split into a head (here) and a tail (c's helper) when split_point says
 // so.  d_data is already ordered on c's stream (caller data, or the slot's input after stream_in).
-static int submit_split(bw_ctx* c, Slot& s, const uint8_t* d_data, uint64_t data_len, const uint64_t* foff,
-                        const uint64_t* flen, uint64_t nf, const bw_params* prm) {
+static int submit_split(bw_ctx* c, Slot& s, const uint8_t* d_data, BatchPlan& pl) {
     s.tail_ticket = 0;
-    Masks mk;
-    if (int rc = validate_batch(c, data_len, foff, flen, nf, prm, &mk)) return rc;
-    const uint64_t f0 = split_point(c, data_len, flen, nf, prm);
-    if (!f0) return submit(c, s, d_data, data_len, foff, flen, nf, prm);
+    const uint64_t f0 = split_point(c, pl);
+    if (!f0) return submit(c, s, d_data, pl);
+    BatchPlan head = pl.files(0, f0), tail = pl.files(f0, pl.nf - f0);
     if (int rc = ensure_helper(c)) return rc;
     bw_ctx* h = c->helper;
     HIPCHK(c, hipEventRecord(c->e_split, c->stream));  // the tail sees what the caller ordered before
-    if (int rc = submit(c, s, d_data, data_len, foff, flen, f0, prm, true, true)) return rc;
+    if (int rc = submit(c, s, d_data, head, true, true)) return rc;
     HIPCHK(c, hipStreamWaitEvent(h->stream, c->e_split, 0));
     uint64_t t2 = 0;
     Slot& s2 = claim_slot(h, &t2);
-    if (int rc = submit(h, s2, d_data, data_len, foff + f0, flen + f0, nf - f0, prm, true, true)) {
+    if (int rc = submit(h, s2, d_data, tail, true, true)) {
         s2.ticket = 0;
         c->err = "tail part: " + h->err;
         return rc;
@@ -1253,8 +1058,11 @@ extern "C" int bw_submit_device(bw_ctx* c, const uint8_t* d_data, uint64_t data_
     prm = params_or_default(prm, &def);
     hipSetDevice(c->device);
     Slot& s = claim_slot(c, ticket);
-    if (int rc = submit_split(c, s, d_data, data_len, foff, flen, nf, prm)) {
-        s.ticket = 0;
+    BatchPlan pl;
+    int rc = pl.init(data_len, foff, flen, nf, prm, &c->err);
+    if (!rc) rc = submit_split(c, s, d_data, pl);
+    if (rc) {
+        s.ticket = s.tail_ticket = 0;
         if (ticket) *ticket = 0;
         return rc;
     }
@@ -1313,12 +1121,12 @@ extern "C" int bw_submit_host(bw_ctx* c, const uint8_t* data, uint64_t data_len,
     if (ticket) *ticket = 0;
     bw_params def;
     prm = params_or_default(prm, &def);
-    Masks mk;
-    if (int rc = validate_batch(c, data_len, foff, flen, nf, prm, &mk)) return rc;
+    BatchPlan pl;  // a bad batch is refused before it claims a slot or copies anything
+    if (int rc = pl.init(data_len, foff, flen, nf, prm, &c->err)) return rc;
     hipSetDevice(c->device);
     Slot& s = claim_slot(c, ticket);
     int rc = stream_in(c, s, data, data_len);
-    if (!rc) rc = submit_split(c, s, P<uint8_t>(s.input), data_len, foff, flen, nf, prm);
+    if (!rc) rc = submit_split(c, s, P<uint8_t>(s.input), pl);
     if (rc) {
         s.ticket = 0;
         if (ticket) *ticket = 0;
@@ -1455,7 +1263,9 @@ static int submit_sync(bw_ctx* c, uint64_t data_len, const uint64_t* foff, const
                        const bw_params* prm, bool stage = true) {
     Slot& s = c->sync_slot;
     s.ticket = 0;
-    return submit(c, s, P<uint8_t>(c->data), data_len, foff, flen, nf, prm, stage);
+    BatchPlan pl;
+    if (int rc = pl.init(data_len, foff, flen, nf, prm, &c->err)) return rc;
+    return submit(c, s, P<uint8_t>(c->data), pl, stage);
 }
 
 extern "C" int bw_process_files(bw_ctx* c, const uint8_t* data, uint64_t data_len, const uint64_t* foff,
@@ -1484,7 +1294,7 @@ extern "C" int bw_fastcdc_chunks(bw_ctx* c, const uint8_t* src, uint64_t len, ui
     p.flags = BW_F_NO_HASH;
     p.small_file_threshold = 0;
     const uint64_t off = 0;
-    std::vector<bw_blob> tmp(len / std::min<uint64_t>(mk.s0, mk.max) + 2);
+    std::vector<bw_blob> tmp(chunk_bound(mk, len));
     uint64_t n = 0;
     if (int rc = bw_process_files(c, src, len, &off, &len, 1, &p, tmp.data(), tmp.size(), &n)) return rc;
     *n_out = n;

@@ -819,7 +819,8 @@ extern "C" int bw_fastcdc_chunks_hashed(bw_ctx* c, const uint8_t* src, uint64_t 
     p.flags = BW_F_NO_DEDUP;  // chunk + hash; the gate stays the caller's (add_blob)
     p.small_file_threshold = 0;
     const uint64_t off = 0;
-    std::vector<bw_blob> tmp(len / std::min<uint64_t>(2 * (mn / 2), mx) + 2);
+    Masks mk;  // (avg > max passes the asserts above: bw_process_files refuses it below, with its message)
+    std::vector<bw_blob> tmp(make_masks(mn, av, mx, &mk) ? 0 : chunk_bound(mk, len));
     uint64_t n = 0;
     // the file goes up as one pageable hipMemcpy, not through the context's pinned staging ring: the
     // reference's tasks call this from many threads at once (one mmap'd file each), and 16 callers

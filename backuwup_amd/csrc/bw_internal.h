@@ -1,13 +1,8 @@
 // bw_internal.h -- host-side declarations shared by the backuwup_amd translation units.
 #pragma once
-#include <algorithm>
-#include <string>
-#include <thread>
-#include <vector>
 #include <hip/hip_runtime.h>
-#include <stdint.h>
 
-#include "../../include/backuwup_gpu.h"
+#include "bw_plan.h"  // the C ABI header, Masks, the table descriptors, tile and chain constants, parallel_ranges
 
 // BW_DIAG: compile the variants measured slower than the shipped path (the 8-wave scan, the
 // prefetch / block-pair leaf loaders, the upper levels fused into the leaf pass, the split batch,
@@ -22,22 +17,15 @@ namespace bw {
 
 // ------------------------------------------------------------------ tunables
 constexpr int SCAN_BLOCK = 1024;                                   // 16 waves, 1 block per CU (LDS)
-#ifndef BW_SCAN_STRIP
-#define BW_SCAN_STRIP 2048
-#endif
 #ifndef BW_SCAN_CAP
 #define BW_SCAN_CAP 16
 #endif
-constexpr int SCAN_STRIP = BW_SCAN_STRIP;                          // bytes per lane
-constexpr uint64_t SCAN_TILE = 64ull * SCAN_STRIP;                 // one wave's sub-tile (128 KiB)
 constexpr int SCAN_STRIP_SMALL = SCAN_STRIP / 2;                   // batches below SCAN_SMALL_BYTES
 constexpr uint64_t SCAN_SMALL_BYTES = 4ull << 30;                  // (one tile per wave otherwise: slow)
-constexpr uint32_t SCAN_TILE_SHIFT = __builtin_ctzll(SCAN_TILE);
 constexpr int SCAN_CAP = BW_SCAN_CAP;                              // candidate slots per tile
 constexpr int SCAN_STEP = 64;                                      // bytes per lane per staged step
 constexpr int STAGE_ROW = SCAN_STEP + 16;                          // padded LDS staging row
 constexpr int GEAR_REP = 32;                                      // LDS gear replicas
-constexpr int CHAIN_CAP = 128;                                    // cuts stored per segment
 
 // device counter slots (uint64 each)
 enum Ctr : int {
@@ -64,36 +52,6 @@ enum Ctr : int {
 };
 static_assert(SCAN_STRIP_SMALL % (4 * SCAN_STEP) == 0, "k_scan consumes four 64-byte steps per iteration");
 static_assert(SCAN_STRIP % (4 * SCAN_STEP) == 0, "k_scan consumes four 64-byte steps per iteration");
-
-struct Masks {
-    uint32_t min, avg, max, s0;  // s0 = 2 * (min / 2): first position the crate hashes
-    uint64_t mask_s, mask_l, mask_pre;  // mask_pre = mask_s & mask_l (scan prefilter)
-    uint32_t pre_shift;  // the scan carries h << pre_shift; 63 - top bit of (mask_s | mask_l)
-    uint32_t pre_hi;     // bits of mask_pre inside the high dword of h << pre_shift
-    uint32_t tile_shift; // log2 of the scan tile in bytes (SCAN_TILE, or half of it for small batches)
-};
-
-// One boundary-resolution segment: a window [start, end) of one CDC file.
-struct SegDesc {
-    uint64_t start, end, file_end;
-    uint32_t cfile;  // index among the batch's CDC files
-    uint32_t last;   // 1 = last segment of its file
-};
-
-struct CFileDesc {
-    uint64_t start, end;  // global byte range of the file
-    uint64_t fb_off;      // offset into the serial-walker output buffer
-    uint32_t first_seg, nseg;
-};
-
-// Canonical-order unit: either a whole small file (kind 0) or one CDC segment (kind 1).
-struct UnitDesc {
-    uint64_t start, len;  // small file: its range; segment: unused
-    uint32_t file;        // batch file index
-    uint32_t kind;        // 0 = small-file blob, 1 = CDC segment
-    uint32_t seg;         // segment index (kind 1)
-    uint32_t cfile;       // CDC file index (kind 1)
-};
 
 // Blob table (struct of arrays), canonical order.
 struct BlobArrays {
@@ -246,24 +204,6 @@ uint32_t zstd_window_descriptor(uint64_t raw_len);
 constexpr int GF_ROW_TILE = 8;             // k_gf_matmul: destination rows accumulated per pass over the sources
 constexpr uint32_t GF_WAVE_BYTES = 2048;   // bytes of every destination row one wave task covers (16 per lane and step)
 constexpr uint32_t GF_GRID_BLOCKS = 1024;  // blocks of 4 waves per launch: a grid pass covers 4096 wave tasks
-
-// ------------------------------------------------------------------ host helpers
-// fn(lo, hi) over [0, n) on up to 16 threads: the host-side table work of million-item batches
-// (16 = this GPU's share of the box's cores).  `work` (default n) sizes the thread count; small
-// work runs inline.
-template <typename F>
-void parallel_ranges(uint64_t n, F fn, uint64_t work = 0) {
-    if (!work) work = n;
-    const uint64_t hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    const uint64_t t = work < 65536 ? 1 : std::min<uint64_t>(std::min<uint64_t>(hw, work / 32768), n);
-    if (t <= 1) {
-        fn(0, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (uint64_t k = 0; k < t; k++) th.emplace_back(fn, n * k / t, n * (k + 1) / t);
-    for (auto& x : th) x.join();
-}
 
 // ------------------------------------------------------------------ many small messages (bw_capi.hip)
 int ctx_device(const bw_ctx* c);

@@ -59,8 +59,10 @@ int chunk_from(bw_ctx* c, const uint8_t* d_window, uint64_t lo, uint64_t hi, uin
     const uint64_t mis = at & 15;  // the library reads from 16-byte aligned batch pointers
     const uint8_t* base = (const uint8_t*)(at - mis);
     const uint64_t flen = hi - start, foff = mis;
+    Masks mk;
+    if (int rc = make_masks(p.min_size, p.avg_size, p.max_size, &mk)) return rc;
     if (int rc = bw_submit_device(c, base, mis + flen, &foff, &flen, 1, &p, &ch.ticket)) return rc;
-    const uint64_t cap = flen / std::min<uint64_t>(2 * (p.min_size / 2), p.max_size) + 2;
+    const uint64_t cap = chunk_bound(mk, flen);
     if (tmp.size() < cap) tmp.resize(cap);
     uint64_t n = 0;
     if (int rc = bw_wait(c, ch.ticket, tmp.data(), tmp.size(), &n)) return rc;
