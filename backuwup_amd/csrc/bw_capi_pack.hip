@@ -431,21 +431,11 @@ extern "C" uint64_t bw_zstd_store_size(uint64_t len) {
 // ------------------------------------------------------------------ packfiles (§8f row 4)
 // Manager::write_packfiles / serialize_packfile (pack.rs:115-227); kernels in bw_pack.hip.
 
-static uint32_t varint_len(uint64_t v) { return v < 251 ? 1 : (v < (1ull << 16) ? 3 : (v < (1ull << 32) ? 5 : 9)); }
-
 static uint64_t sealed_len_of(uint64_t payload, uint32_t flags) {
     return (flags & BW_PACK_ZSTD_STORE ? bw_zstd_store_size(payload) : payload) + BW_SEAL_TAG_BYTES;
 }
 
 // header plaintext bytes of a PackfileHeaderBlob entry
-static uint64_t entry_len(uint64_t sealed, uint64_t section_off) {
-    return 32 + 1 + 1 + varint_len(sealed) + varint_len(section_off);
-}
-
-// prune (bw_prune.hip) lays out headers of its own with the same sizes
-uint32_t bw::pack_varint_len(uint64_t v) { return varint_len(v); }
-uint64_t bw::pack_entry_len(uint64_t sealed, uint64_t section_off) { return entry_len(sealed, section_off); }
-
 // write_packfiles' drain (pack.rs:123-148) over queue positions [i, to): packfiles close when their
 // blob section reaches PACKFILE_TARGET_SIZE or PACKFILE_MAX_BLOBS blobs; the last may be a remainder.
 static void plan_range(const uint64_t* payload_len, uint64_t i, uint64_t to, uint32_t flags,
@@ -456,13 +446,13 @@ static void plan_range(const uint64_t* payload_len, uint64_t i, uint64_t to, uin
         uint64_t written = 0, hdr = 0;
         while (i < to) {
             const uint64_t sealed = sealed_len_of(payload_len[i], flags);
-            hdr += entry_len(sealed, written);
+            hdr += pack_entry_len(sealed, written);
             written += sealed + BW_BLOB_NONCE_SIZE;
             p.n_blobs++;
             i++;
             if (written >= BW_PACKFILE_TARGET_SIZE || p.n_blobs >= BW_PACKFILE_MAX_BLOBS) break;
         }
-        hdr += varint_len(p.n_blobs);
+        hdr += pack_varint_len(p.n_blobs);
         p.header_len = hdr + BW_SEAL_TAG_BYTES;
         p.offset = off;
         p.size = 8 + p.header_len + written;
@@ -495,10 +485,10 @@ static bool plan_valid(const uint64_t* payload_len, uint64_t n, uint32_t flags, 
                 return false;
             }
             const uint64_t sealed = sealed_len_of(payload_len[f.first_blob + k], flags);
-            hdr += entry_len(sealed, written);
+            hdr += pack_entry_len(sealed, written);
             written += sealed + BW_BLOB_NONCE_SIZE;
         }
-        const uint64_t header_len = hdr + varint_len(f.n_blobs) + BW_SEAL_TAG_BYTES;
+        const uint64_t header_len = hdr + pack_varint_len(f.n_blobs) + BW_SEAL_TAG_BYTES;
         if (f.header_len != header_len || f.size != 8 + header_len + written) {
             why = "packfile " + std::to_string(p) + " sizes do not match its blobs";
             return false;
@@ -638,8 +628,8 @@ static int pack_submit(bw_ctx* c, const uint8_t* prk, const uint8_t* d_src, cons
         [&](uint64_t p_lo, uint64_t p_hi) {
             for (uint64_t p = p_lo; p < p_hi; p++) {
                 const bw_packfile& f = plan[p];
-                uint64_t entry = h_off[p] + varint_len(f.n_blobs), section = 0;
-                const uint64_t data0 = f.offset + 8 + f.header_len;
+                uint64_t entry = h_off[p] + pack_varint_len(f.n_blobs), section = 0;
+                const uint64_t data0 = section_base(f);
                 for (uint64_t i = f.first_blob; i < f.first_blob + f.n_blobs; i++) {
                     const uint64_t frame = store ? bw_zstd_store_size(src_len[i]) : src_len[i];
                     const uint64_t sealed = frame + BW_SEAL_TAG_BYTES;
@@ -651,7 +641,7 @@ static int pack_submit(bw_ctx* c, const uint8_t* prk, const uint8_t* d_src, cons
                     b.section_off = section;
                     b.hdr_off = entry;
                     b.nonce_off = data0 + section;
-                    entry += entry_len(sealed, section);
+                    entry += pack_entry_len(sealed, section);
                     section += sealed + BW_BLOB_NONCE_SIZE;
                     s_len[i] = frame;
                     s_off[i] = src_off[i];
@@ -822,7 +812,7 @@ extern "C" int bw_index_files_build(bw_ctx* c, const uint8_t prk[32], const uint
     for (uint64_t f = 0; f < nf; f++) {
         const uint64_t cnt = f + 1 < nf ? BW_INDEX_MAX_FILE_ENTRIES : n - f * BW_INDEX_MAX_FILE_ENTRIES;
         pt_off[f] = pt;
-        pt_len[f] = varint_len(cnt) + BW_INDEX_ENTRY_BYTES * cnt;
+        pt_len[f] = pack_varint_len(cnt) + BW_INDEX_ENTRY_BYTES * cnt;
         tab[f] = bw_index_file{(uint32_t)(last_file_num + 1 + f), 0, off, pt_len[f] + BW_SEAL_TAG_BYTES, cnt};
         dst_off[f] = off;
         pt += pt_len[f];
@@ -863,7 +853,8 @@ extern "C" int bw_index_load_files(bw_ctx* c, const uint8_t prk[32], const uint8
     if (bad_file) *bad_file = ~0ull;
     if (!nf) return BW_OK;
     hipSetDevice(c->device);
-    uint64_t end = 0, pt_total = 0;
+    const uint64_t end = store_extent(files, nf);
+    uint64_t pt_total = 0;
     std::vector<uint64_t> src_off(nf), src_len(nf), pt_off(nf), pt_len(nf);
     std::vector<uint8_t> nonces(12 * nf), info(5 * nf);
     for (uint64_t f = 0; f < nf; f++) {
@@ -874,7 +865,6 @@ extern "C" int bw_index_load_files(bw_ctx* c, const uint8_t prk[32], const uint8
         }
         src_off[f] = files[f].offset;
         src_len[f] = files[f].size;
-        end = std::max(end, files[f].offset + files[f].size);
         pt_off[f] = pt_total;
         pt_len[f] = files[f].size - BW_SEAL_TAG_BYTES;
         pt_total += (pt_len[f] + 15) & ~15ull;
@@ -1115,41 +1105,36 @@ int bw::unpack_blobs_core(bw_ctx* c, const uint8_t* prk, const uint8_t* d_pf, co
     hipSetDevice(c->device);
     if (d_len) HIPCHK(c, hipMemsetAsync(d_len, 0, n * 8, c->stream));
     // the blobs whose nonce and sealed bytes lie inside their packfile (read_exact, unpack.rs:58-59)
-    std::vector<uint64_t> idx, s_off, s_len, f_off;
+    std::vector<uint64_t> idx, n_off, s_off, s_len, f_off;
     uint64_t stage = 0;
     for (uint64_t i = 0; i < n; i++) {
         const bw_unpack_entry& e = entries[i];
         const bw_packfile& f = pf[e.packfile];
         out_len[i] = 0;
-        const uint64_t base = 8 + f.header_len;
         if (!rs_range_ok(f.size, f.header_len, e.offset, e.length)) {
             status[i] = BW_UNPACK_ERANGE;
             continue;
         }
         status[i] = BW_UNPACK_OK;
         idx.push_back(i);
-        s_off.push_back(f.offset + base + e.offset + BW_BLOB_NONCE_SIZE);
+        n_off.push_back(blob_place(f, e).nonce);
+        s_off.push_back(blob_place(f, e).sealed);
         s_len.push_back(e.length);
         f_off.push_back(stage);
         stage += (e.length - BW_SEAL_TAG_BYTES + 15) & ~15ull;
     }
     const uint64_t m = idx.size();
     if (!m) return BW_OK;
-    // the nonces come out of the packfiles: 12 bytes each, behind the staged frames
+    // The staging area serves twice.  First the nonces come out of the packfiles through it; the fetch
+    // is synchronous, so they are on the host before the first frame is opened into it, from 0.  It is
+    // sized as before (frames, then 12 bytes per nonce behind them), which covers the fetch's 20 bytes
+    // per blob for any blob with a payload byte; the fetch grows it otherwise.
     c->pk_stage_off.clear();  // frames bw_pack_compress_device staged here are gone
     c->pk_stage_len.clear();
-    const uint64_t nonce_base = (stage + 255) & ~255ull;
-    if (int rc = ensure(c, c->pk_stage, nonce_base + 12 * m + 16)) return rc;
-    uint8_t* stg = P<uint8_t>(c->pk_stage);
-    std::vector<uint64_t> n_off(m);
-    for (uint64_t k = 0; k < m; k++) n_off[k] = s_off[k] - BW_BLOB_NONCE_SIZE;
-    if (int rc = ensure(c, c->ix_tab, m * 8)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->ix_tab.p, n_off.data(), m * 8, hipMemcpyHostToDevice, c->stream));
-    launch_gather12(c->stream, d_pf, P<uint64_t>(c->ix_tab), m, stg + nonce_base);
-    HIPCHK(c, hipGetLastError());
+    if (int rc = ensure(c, c->pk_stage, ((stage + 255) & ~255ull) + 12 * m + 16)) return rc;
     std::vector<uint8_t> nonces(12 * m), hashes(32 * m), ok(m);
-    HIPCHK(c, hipMemcpyAsync(nonces.data(), stg + nonce_base, 12 * m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = rs_fetch_nonces(c, d_pf, n_off.data(), m, c->pk_stage, nonces.data())) return rc;
+    uint8_t* stg = P<uint8_t>(c->pk_stage);
     for (uint64_t k = 0; k < m; k++) memcpy(&hashes[32 * k], entries[idx[k]].hash, 32);
     SealJob j = seal_job(SealMode::Open, prk, s_off.data(), s_len.data(), m, hashes.data(), 32, nonces.data(), f_off.data(),
                          ok.data());
@@ -1221,8 +1206,7 @@ extern "C" int bw_unpack_blobs(bw_ctx* c, const uint8_t prk[32], const uint8_t* 
     if (n && (!data || !pf || !npf || !entries || !dst || !dst_off || !out_len || !status)) return BW_EINVAL;
     if (!n) return BW_OK;
     hipSetDevice(c->device);
-    uint64_t end = 0;
-    for (uint64_t p = 0; p < npf; p++) end = std::max(end, pf[p].offset + pf[p].size);
+    const uint64_t end = store_extent(pf, npf);
     std::vector<uint64_t> dof(n);
     for (uint64_t i = 0; i < n; i++) dof[i] = i * (uint64_t)BW_BLOB_MAX_UNCOMPRESSED_SIZE;
     if (int rc = ensure(c, c->pk_out, end + 16)) return rc;

@@ -15,7 +15,6 @@
 #include "bw_device.h"
 #include "bw_internal.h"
 #include "bw_ctx.h"
-#include "bw_unpack.h"
 #include "bw_restore.h"
 #include "bw_prune.h"
 #include "bw_check.h"
@@ -206,16 +205,14 @@ extern "C" int bw_check_structure(bw_restore* s, uint8_t* entry_flags, uint8_t* 
                    total = at_ist + ck_up16(n_i);
     if (int rc = ensure(c, s->ck_buf, total + 16)) return rc;
     uint8_t* b = P<uint8_t>(s->ck_buf);
-    std::vector<PrPackfile> hpf(n_pf);
-    for (uint64_t p = 0; p < n_pf; p++) hpf[p] = PrPackfile{s->pf[p].size, s->pf[p].header_len};
+    const std::vector<PrPackfile> hpf = rs_packfile_table(s);
     if (n_pf) {
         HIPCHK(c, hipMemsetAsync(b + at_sums, 0, sum_bytes, c->stream));
         HIPCHK(c, hipMemcpyAsync(b + at_pf, hpf.data(), n_pf * sizeof(PrPackfile), hipMemcpyHostToDevice, c->stream));
     }
     if (n_e) HIPCHK(c, hipMemsetAsync(b + at_owner, 0xff, 4 * n_e, c->stream));
 
-    const RsLocator loc{P<uint8_t>(s->items),      P<uint32_t>(s->item_tab), P<uint32_t>(s->item_pos), P<bw_unpack_entry>(s->d_entries),
-                        P<uint32_t>(s->entry_tab), n_i ? s->item_cap : 0,    n_e ? s->entry_cap : 0};
+    const RsLocator loc = rs_locator(s);
     uint32_t* owner = (uint32_t*)(b + at_owner);
     launch_check_scan(c->stream, loc.entries, n_e, (uint64_t*)(b + at_excl), b + at_open, (uint64_t*)(b + at_bsum),
                       (uint32_t*)(b + at_bhead), (uint64_t*)(b + at_carry));
@@ -269,20 +266,13 @@ static int ck_auth(bw_restore* s, const std::vector<uint64_t>& idx, uint8_t* sta
     std::vector<uint8_t> hashes(32 * m), nonces(12 * m), ok(m);
     for (uint64_t k = 0; k < m; k++) {
         const bw_unpack_entry& e = s->entries[idx[k]];
-        const bw_packfile& f = s->pf[e.packfile];
-        n_off[k] = f.offset + 8 + f.header_len + e.offset;
-        s_off[k] = n_off[k] + BW_BLOB_NONCE_SIZE;
+        const BlobPlace at = blob_place(s->pf[e.packfile], e);
+        n_off[k] = at.nonce;
+        s_off[k] = at.sealed;
         s_len[k] = e.length;
         memcpy(&hashes[32 * k], e.hash, 32);
     }
-    // the nonces come out of the packfiles, 12 bytes each (as the unpack chain fetches them)
-    if (int rc = ensure(c, s->ck_buf, 8 * m + 12 * m + 16)) return rc;
-    uint8_t* b = P<uint8_t>(s->ck_buf);
-    HIPCHK(c, hipMemcpyAsync(b, n_off.data(), 8 * m, hipMemcpyHostToDevice, c->stream));
-    launch_gather12(c->stream, s->d_pf, (const uint64_t*)b, m, b + 8 * m);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(nonces.data(), b + 8 * m, 12 * m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = rs_fetch_nonces(c, s->d_pf, n_off.data(), m, s->ck_buf, nonces.data())) return rc;
     if (int rc = bw_auth_device(c, s->prk, s->d_pf, s_off.data(), s_len.data(), m, hashes.data(), 32, nonces.data(), ok.data()))
         return rc;
     for (uint64_t k = 0; k < m; k++) status[idx[k]] = ok[k] ? BW_UNPACK_OK : BW_UNPACK_ETAG;
@@ -292,29 +282,22 @@ static int ck_auth(bw_restore* s, const std::vector<uint64_t>& idx, uint8_t* sta
 // FULL: the unpack chain with BW_UNPACK_VERIFY, `slots` blobs at a time; tree blobs that pass are parsed in their slots
 static int ck_full(bw_restore* s, const std::vector<uint64_t>& idx, uint8_t* status) {
     bw_ctx* c = s->c;
-    std::vector<uint64_t> eidx, off, blen;
+    std::vector<uint64_t> eidx;
     std::vector<uint8_t> bst;
     std::vector<RsTreeHdr> hd;
     for (uint64_t lo = 0; lo < idx.size(); lo += s->slots) {
         const uint64_t m = std::min<uint64_t>(s->slots, idx.size() - lo);
         eidx.assign(idx.begin() + lo, idx.begin() + lo + m);
-        off.resize(m);
-        for (uint64_t k = 0; k < m; k++) off[k] = k * RS_SLOT_STRIDE;
         RsTables t;
-        if (int rc = rs_tables(s, m, m, t)) return rc;
-        if (int rc = rs_decode(s, eidx, off, BW_UNPACK_VERIFY, t, blen, bst)) return rc;
+        if (int rc = rs_tree_decode(s, eidx, BW_UNPACK_VERIFY, m, t, bst)) return rc;
         bool trees = false;
         for (uint64_t k = 0; k < m; k++) {
             status[eidx[k]] = bst[k];
             trees = trees || (!bst[k] && s->entries[eidx[k]].kind == BW_BLOB_TREE);
         }
-        if (trees) {  // a blob the chain refused has length 0 on the device: the parser reads nothing of it
-            if (int rc = ensure(c, s->q, m * sizeof(RsTreeHdr) + 16)) return rc;
-            launch_rs_tree_parse(c->stream, P<uint8_t>(s->slot_buf), t.slot_off, t.slot_len, m, P<RsTreeHdr>(s->q));
-            HIPCHK(c, hipGetLastError());
-            hd.resize(m);
-            HIPCHK(c, hipMemcpyAsync(hd.data(), s->q.p, m * sizeof(RsTreeHdr), hipMemcpyDeviceToHost, c->stream));
-        }
+        // a blob the chain refused has length 0 on the device: the parser reads nothing of it
+        if (trees)
+            if (int rc = rs_tree_parse(s, t, m, &hd)) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the slots and the tables are reused by the next sub-batch
         if (trees)
             for (uint64_t k = 0; k < m; k++)

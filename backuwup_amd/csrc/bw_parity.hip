@@ -15,6 +15,7 @@
 #include "bw_device.h"
 #include "bw_internal.h"
 #include "bw_ctx.h"
+#include "bw_store_layout.h"
 
 using namespace bw;
 
@@ -426,8 +427,7 @@ extern "C" int bw_parity_build(bw_ctx* c, const uint8_t* data, const bw_packfile
                                uint8_t* digests) {
     if (!c || !n_groups || !groups || !pf || !n_pf || !data || !out || !digests) return BW_EINVAL;
     hipSetDevice(c->device);
-    uint64_t end = 0;
-    for (uint64_t p = 0; p < n_pf; p++) end = std::max(end, pf[p].offset + pf[p].size);
+    const uint64_t end = store_extent(pf, n_pf);
     const uint64_t at = (end + 255) & ~255ull;
     if (int rc = ensure(c, c->gf_io, at + out_cap + 16)) return rc;
     uint8_t* b = P<uint8_t>(c->gf_io);

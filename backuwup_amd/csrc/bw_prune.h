@@ -16,11 +16,6 @@ constexpr uint32_t PR_QUEUED = 2;  // a tree reference reached it: it is, or was
 constexpr uint32_t PR_EXPAND_Y = 4;  // workgroups that share one tree blob's references
 constexpr uint64_t PR_ERR_DEVICE = 65536;  // records of the device error list of a first walk (5 MiB)
 
-// What the range check needs of a packfile.
-struct PrPackfile {
-    uint64_t size, header_len;
-};
-
 // counters of a walk
 enum { PR_C_NEXT = 0, PR_C_ERRORS = 1, PR_C_EXPANDED = 2, PR_C_COUNT = 4 };
 

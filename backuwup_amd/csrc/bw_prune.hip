@@ -179,8 +179,7 @@ static int pr_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, u
     if (int rc = ensure(c, s->pr_err, dev_cap * sizeof(bw_prune_error) + 16)) return rc;
     if (int rc = ensure(c, s->pr_stat, pf_at + n_pf * sizeof(PrPackfile) + 16)) return rc;
     if (int rc = ensure(c, s->q, std::max<uint64_t>(32 * n_roots, sizeof(RsTreeHdr) * (uint64_t)s->slots) + 16)) return rc;
-    std::vector<PrPackfile> hpf(n_pf);
-    for (uint64_t p = 0; p < n_pf; p++) hpf[p] = PrPackfile{s->pf[p].size, s->pf[p].header_len};
+    const std::vector<PrPackfile> hpf = rs_packfile_table(s);
     uint8_t* d_stat = P<uint8_t>(s->pr_stat);
     HIPCHK(c, hipMemsetAsync(s->pr_bits.p, 0, 4 * words + 16, c->stream));
     HIPCHK(c, hipMemsetAsync(s->pr_ctr.p, 0, 8 * PR_C_COUNT, c->stream));
@@ -189,8 +188,7 @@ static int pr_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, u
     if (n_roots) HIPCHK(c, hipMemcpyAsync(s->q.p, roots, 32 * n_roots, hipMemcpyHostToDevice, c->stream));
 
     PrWalk w;
-    w.loc = RsLocator{P<uint8_t>(s->items),       P<uint32_t>(s->item_tab),  P<uint32_t>(s->item_pos), P<bw_unpack_entry>(s->d_entries),
-                      P<uint32_t>(s->entry_tab),  s->n_items ? s->item_cap : 0, n_e ? s->entry_cap : 0};
+    w.loc = rs_locator(s);
     w.pf = (const PrPackfile*)(d_stat + pf_at);
     w.bits = P<uint32_t>(s->pr_bits);
     w.ctr = P<uint64_t>(s->pr_ctr);
@@ -202,7 +200,7 @@ static int pr_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, u
     HIPCHK(c, hipGetLastError());
 
     std::vector<bw_prune_error> herr;  // what the chain refused: the host knows it first
-    std::vector<uint64_t> fr, eidx, off, blen;
+    std::vector<uint64_t> fr, eidx;
     std::vector<uint8_t> bst;
     std::vector<uint32_t> cst;
     uint64_t n_front = 0, n_levels = 0;
@@ -224,17 +222,13 @@ static int pr_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, u
         for (uint64_t lo = 0; lo < n_front; lo += s->slots) {
             const uint64_t m = std::min<uint64_t>(s->slots, n_front - lo);
             eidx.assign(fr.begin() + lo, fr.begin() + lo + m);
-            off.resize(m);
-            for (uint64_t k = 0; k < m; k++) {
+            for (uint64_t k = 0; k < m; k++)
                 if (eidx[k] >= n_e) {
                     c->err = "prune: a frontier names an entry outside the table";
                     return BW_EHIP;
                 }
-                off[k] = k * RS_SLOT_STRIDE;
-            }
             RsTables t;
-            if (int rc = rs_tables(s, m, m, t)) return rc;  // the first instance words hold the chain statuses
-            if (int rc = rs_decode(s, eidx, off, flags, t, blen, bst)) return rc;
+            if (int rc = rs_tree_decode(s, eidx, flags, m, t, bst)) return rc;  // the first instance words hold the chain statuses
             cst.assign(m, 0);
             for (uint64_t k = 0; k < m; k++)
                 if (bst[k]) {
@@ -243,7 +237,7 @@ static int pr_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, u
                 }
             uint32_t* d_cst = (uint32_t*)t.dst_off;
             HIPCHK(c, hipMemcpyAsync(d_cst, cst.data(), 4 * m, hipMemcpyHostToDevice, c->stream));
-            launch_rs_tree_parse(c->stream, P<uint8_t>(s->slot_buf), t.slot_off, t.slot_len, m, P<RsTreeHdr>(s->q));
+            if (int rc = rs_tree_parse(s, t, m, nullptr)) return rc;  // the headers stay in s->q, sized above
             launch_prune_expand(c->stream, w, d_front + lo, P<uint8_t>(s->slot_buf), t.slot_off, P<RsTreeHdr>(s->q), d_cst, m);
             HIPCHK(c, hipGetLastError());
             // the slots and the tables are reused by the next sub-batch
@@ -418,55 +412,29 @@ extern "C" int bw_prune_repack_device(bw_restore* s, const uint64_t* order, uint
     }
     if (!n) return BW_OK;
 
-    // tables: order | sect | hoff | src | dst | len | piece0 (n + 1), then one PackFileDesc per packfile
-    std::vector<uint64_t> tab(7 * n + 1);
-    uint64_t *t_order = tab.data(), *t_sect = t_order + n, *t_hoff = t_sect + n, *t_src = t_hoff + n, *t_dst = t_src + n,
-             *t_len = t_dst + n, *t_pc = t_len + n;
+    // the tables (repack_tables' columns), then one PackFileDesc per packfile
+    const RepackTables r = repack_tables(order, n, plan, npf, s->pf.data(), s->entries.data());
     std::vector<PackFileDesc> files(npf);
-    std::vector<uint64_t> h_off(npf), h_len(npf), h_dst(npf);
-    uint64_t hdr_total = 0, pieces = 0;
-    for (uint64_t p = 0; p < npf; p++) {
-        const bw_packfile& f = plan[p];
-        h_off[p] = hdr_total;
-        h_len[p] = f.header_len - BW_SEAL_TAG_BYTES;
-        h_dst[p] = f.offset + 8;
-        files[p] = PackFileDesc{hdr_total, f.n_blobs, f.offset, f.header_len};
-        uint64_t entry = hdr_total + pack_varint_len(f.n_blobs), section = 0;
-        const uint64_t data0 = f.offset + 8 + f.header_len;
-        for (uint64_t i = f.first_blob; i < f.first_blob + f.n_blobs; i++) {
-            const bw_unpack_entry& e = s->entries[order[i]];
-            const bw_packfile& old = s->pf[e.packfile];
-            t_order[i] = order[i];
-            t_sect[i] = section;
-            t_hoff[i] = entry;
-            t_src[i] = old.offset + 8 + old.header_len + e.offset;
-            t_dst[i] = data0 + section;
-            t_len[i] = BW_BLOB_NONCE_SIZE + e.length;
-            t_pc[i] = pieces;
-            pieces += (t_len[i] + RS_PIECE - 1) / RS_PIECE;
-            entry += pack_entry_len(e.length, section);
-            section += e.length + BW_BLOB_NONCE_SIZE;
-        }
-        hdr_total += h_len[p];
-    }
-    t_pc[n] = pieces;
-    const uint64_t tab_bytes = 8 * tab.size();
+    for (uint64_t p = 0; p < npf; p++) files[p] = PackFileDesc{r.h_off[p], plan[p].n_blobs, plan[p].offset, plan[p].header_len};
+    const uint64_t tab_bytes = 8 * r.tab.size();
     if (int rc = ensure(c, s->pr_tab, tab_bytes + npf * sizeof(PackFileDesc) + 16)) return rc;
-    if (int rc = ensure(c, s->pr_hdr, hdr_total + 16)) return rc;
+    if (int rc = ensure(c, s->pr_hdr, r.hdr_total + 16)) return rc;
     uint64_t* d_tab = P<uint64_t>(s->pr_tab);
+    auto d_col = [&](int col) { return d_tab + (uint64_t)col * n; };
     PackFileDesc* d_files = (PackFileDesc*)(P<uint8_t>(s->pr_tab) + tab_bytes);
-    HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tab, r.tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_files, files.data(), npf * sizeof(PackFileDesc), hipMemcpyHostToDevice, c->stream));
     // the header plaintexts, built in place: the entries, then each Vec length and u64 LE prefix (k_pack_files)
-    launch_pack_meta_sealed(c->stream, P<bw_unpack_entry>(s->d_entries), d_tab, d_tab + n, d_tab + 2 * n, n, P<uint8_t>(s->pr_hdr));
+    launch_pack_meta_sealed(c->stream, P<bw_unpack_entry>(s->d_entries), d_col(RP_ORDER), d_col(RP_SECT), d_col(RP_HOFF), n,
+                            P<uint8_t>(s->pr_hdr));
     launch_pack_meta(c->stream, nullptr, 0, d_files, npf, P<uint8_t>(s->pr_hdr), d_out);
-    launch_prune_move(c->stream, s->d_pf, d_tab + 3 * n, d_tab + 4 * n, d_tab + 5 * n, d_tab + 6 * n, n, pieces, d_out);
+    launch_prune_move(c->stream, s->d_pf, d_col(RP_SRC), d_col(RP_DST), d_col(RP_LEN), d_col(RP_PIECE0), n, r.pieces, d_out);
     HIPCHK(c, hipGetLastError());
     // every header: derive_backup_key(b"header") + AES-GCM(new packfile id) behind the length prefix
     std::vector<uint8_t> info(npf * 6);
     for (uint64_t p = 0; p < npf; p++) memcpy(&info[6 * p], "header", 6);
-    if (int rc = bw_seal_device(c, s->prk, P<uint8_t>(s->pr_hdr), h_off.data(), h_len.data(), npf, info.data(), 6, new_ids, d_out,
-                                h_dst.data()))
+    if (int rc = bw_seal_device(c, s->prk, P<uint8_t>(s->pr_hdr), r.h_off.data(), r.h_len.data(), npf, info.data(), 6, new_ids,
+                                d_out, r.h_dst.data()))
         return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BW_OK;
@@ -477,8 +445,7 @@ extern "C" int bw_prune_repack(bw_restore* s, const uint64_t* order, uint64_t n,
     if (!s || (npf && (!plan || !out))) return BW_EINVAL;
     bw_ctx* c = s->c;
     hipSetDevice(c->device);
-    uint64_t total = 0;
-    for (uint64_t p = 0; p < npf; p++) total = std::max(total, plan[p].offset + plan[p].size);
+    const uint64_t total = store_extent(plan, npf);
     if (total > (uint64_t)BW_PACKFILE_MAX_SIZE * std::max<uint64_t>(npf, 1)) return BW_EINVAL;  // checked again below
     if (int rc = ensure(c, s->win, total + 16)) return rc;
     if (int rc = bw_prune_repack_device(s, order, n, plan, npf, new_ids, P<uint8_t>(s->win))) return rc;

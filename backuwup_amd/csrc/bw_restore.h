@@ -9,6 +9,7 @@
 
 #include "../../include/backuwup_gpu.h"
 #include "bw_ctx.h"
+#include "bw_store_layout.h"
 
 struct bw_restore;
 
@@ -16,7 +17,6 @@ namespace bw {
 
 constexpr uint32_t RS_EMPTY = 0xffffffffu;            // a free table slot (tables hold u32 record indices)
 constexpr uint64_t RS_SLOT_STRIDE = BW_BLOB_MAX_UNCOMPRESSED_SIZE + 32;  // a decode slot plus skew and load slack
-constexpr uint32_t RS_PIECE = 32768;                  // bytes of one instance a wave copies
 constexpr uint32_t RS_DEFAULT_SLOTS = 1024;           // 3 GiB of decode room
 constexpr uint64_t RS_MAX_INSTANCES = 1u << 20;       // instances of one sub-batch (bounds the tables)
 
@@ -35,15 +35,6 @@ struct RsTreeHdr {
 struct RsInst {
     uint32_t slot, valid;
 };
-
-
-// BW_UNPACK_ERANGE, the one statement of it (the unpack chain, prune's mark and plan, check): the
-// entry's nonce + sealed bytes lie inside the packfile's blob section, and the sealed bytes hold a tag
-__host__ __device__ static inline bool rs_range_ok(uint64_t size, uint64_t header_len, uint64_t offset, uint64_t length) {
-    const uint64_t base = 8 + header_len;
-    return !(base > size || offset > size - base || BW_BLOB_NONCE_SIZE > size - base - offset ||
-             length > size - base - offset - BW_BLOB_NONCE_SIZE || length < BW_SEAL_TAG_BYTES);
-}
 
 // ------------------------------------------------------------------ device code shared with bw_prune.hip and bw_check.hip
 // The locator's probes (the tables are described in bw_restore.hip) and the body of the piece copy.
@@ -179,9 +170,8 @@ void launch_rs_build_ids(hipStream_t st, const uint8_t* ids, uint64_t n_pf, uint
 void launch_rs_build_items(hipStream_t st, const uint8_t* items, uint64_t n_items, const uint8_t* ids,
                            const uint32_t* id_tab, uint32_t id_cap, uint32_t* item_pos, uint32_t* tab, uint32_t cap);
 void launch_rs_build_entries(hipStream_t st, const bw_unpack_entry* entries, uint64_t n, uint32_t* tab, uint32_t cap);
-void launch_rs_locate(hipStream_t st, const uint8_t* hashes, uint64_t n, const uint8_t* items, const uint32_t* item_tab,
-                      uint32_t item_cap, const uint32_t* item_pos, const bw_unpack_entry* entries,
-                      const uint32_t* entry_tab, uint32_t entry_cap, uint64_t* entry_idx, uint8_t* status);
+void launch_rs_locate(hipStream_t st, const uint8_t* hashes, uint64_t n, const RsLocator& loc, uint64_t* entry_idx,
+                      uint8_t* status);
 // tree blobs: blob b lies at blobs + off[b], len[b] bytes
 void launch_rs_tree_parse(hipStream_t st, const uint8_t* blobs, const uint64_t* off, const uint64_t* len, uint64_t n,
                           RsTreeHdr* out);
@@ -199,11 +189,6 @@ void launch_rs_gather(hipStream_t st, const RsInst* inst, uint64_t n, const uint
                       const uint64_t* slot_len, const uint64_t* dst_off, const uint64_t* piece0, uint8_t* dst,
                       uint64_t dst_cap);
 
-// bw_capi_pack.hip's sizes of a bincode varint and of one PackfileHeaderBlob's plaintext (hash, kind,
-// compression, length, offset), for prune's headers
-uint32_t pack_varint_len(uint64_t v);
-uint64_t pack_entry_len(uint64_t sealed, uint64_t section_off);
-
 // bw_unpack_blobs_device (bw_capi_pack.hip) with the regenerated sizes left on the device as well:
 // d_len (device, n x u64, optional) receives out_len[i] (0 for a blob that failed to open or decode),
 // d_map (device, n x u64) is scratch.
@@ -218,11 +203,35 @@ struct RsTables {
     RsInst* inst;
 };
 
+// What the range check needs of a packfile (prune's mark, check's structure pass).
+struct PrPackfile {
+    uint64_t size, header_len;
+};
+
+// ------------------------------------------------------------------ the session's shared steps (bw_restore.hip)
+RsLocator rs_locator(const bw_restore* s);
+std::vector<PrPackfile> rs_packfile_table(const bw_restore* s);
+
+// The nonces of m blobs out of the packfile buffer, 12 bytes each, to `out` (host; synchronous).
+// n_off[k] is blob k's nonce (blob_place).  The first 20 * m bytes of `scratch` are used (it is grown
+// to hold them); what a caller keeps behind them stays.
+int rs_fetch_nonces(bw_ctx* c, const uint8_t* d_pf, const uint64_t* n_off, uint64_t m, DevBuf& scratch, uint8_t* out);
+
 int rs_tables(bw_restore* s, uint64_t m, uint64_t ni, RsTables& t);
 // m located blobs (entry indices eidx) opened and decoded into the slots at off[k]; sizes on the
 // device in t.slot_len, and with the statuses on the host (synchronous)
 int rs_decode(bw_restore* s, const std::vector<uint64_t>& eidx, const std::vector<uint64_t>& off, uint32_t flags,
               const RsTables& t, std::vector<uint64_t>& out_len, std::vector<uint8_t>& st);
+
+// One sub-batch of a tree walk (restore's, prune's mark, check's FULL pass), in two steps.
+// rs_tree_decode: the m <= slots blobs eidx, blob k into the slot at k * RS_SLOT_STRIDE (rs_tables
+// with ni instance places, then rs_decode); bst[k] = the chain's status.  rs_tree_parse: the parser
+// over those slots, the headers to s->q, and to hd (host) when hd is given.  Without hd the launch is
+// left unchecked: the caller's next kernel reads the headers where they are, and checks both.
+// Neither synchronizes past rs_decode: the caller does, before the slots and the tables are reused.
+int rs_tree_decode(bw_restore* s, const std::vector<uint64_t>& eidx, uint32_t flags, uint64_t ni, RsTables& t,
+                   std::vector<uint8_t>& bst);
+int rs_tree_parse(bw_restore* s, const RsTables& t, uint64_t m, std::vector<RsTreeHdr>* hd);
 
 }  // namespace bw
 

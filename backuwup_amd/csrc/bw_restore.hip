@@ -16,6 +16,7 @@
 #include "bw_device.h"
 #include "bw_internal.h"
 #include "bw_ctx.h"
+#include "bw_unpack.h"
 #include "bw_restore.h"
 
 using namespace bw;
@@ -74,13 +75,11 @@ void bw::launch_rs_build_items(hipStream_t st, const uint8_t* items, uint64_t n_
 void bw::launch_rs_build_entries(hipStream_t st, const bw_unpack_entry* entries, uint64_t n, uint32_t* tab, uint32_t cap) {
     if (n) hipLaunchKernelGGL(k_rs_build_entries, rs_grid(n), dim3(256), 0, st, entries, n, tab, cap);
 }
-void bw::launch_rs_locate(hipStream_t st, const uint8_t* hashes, uint64_t n, const uint8_t* items,
-                          const uint32_t* item_tab, uint32_t item_cap, const uint32_t* item_pos,
-                          const bw_unpack_entry* entries, const uint32_t* entry_tab, uint32_t entry_cap,
-                          uint64_t* entry_idx, uint8_t* status) {
+void bw::launch_rs_locate(hipStream_t st, const uint8_t* hashes, uint64_t n, const RsLocator& L, uint64_t* entry_idx,
+                          uint8_t* status) {
     if (n)
-        hipLaunchKernelGGL(k_rs_locate, rs_grid(n), dim3(256), 0, st, hashes, n, items, item_tab, item_cap, item_pos,
-                           entries, entry_tab, entry_cap, entry_idx, status);
+        hipLaunchKernelGGL(k_rs_locate, rs_grid(n), dim3(256), 0, st, hashes, n, L.items, L.item_tab, L.item_cap, L.item_pos,
+                           L.entries, L.entry_tab, L.entry_cap, entry_idx, status);
 }
 
 // ------------------------------------------------------------------ the tree parser
@@ -413,8 +412,7 @@ extern "C" int bw_restore_open_host(bw_ctx* c, const uint8_t prk[32], const uint
                                     bw_restore** out) {
     if (!c || !prk || !out || (n_pf && (!data || !pf))) return BW_EINVAL;
     hipSetDevice(c->device);
-    uint64_t end = 0;
-    for (uint64_t p = 0; p < n_pf; p++) end = std::max(end, pf[p].offset + pf[p].size);
+    const uint64_t end = store_extent(pf, n_pf);
     DevBuf buf;
     if (int rc = ensure(c, buf, end + 16)) return rc;
     hipError_t e = end ? hipMemcpy(buf.p, data, end, hipMemcpyHostToDevice) : hipSuccess;
@@ -429,6 +427,33 @@ extern "C" int bw_restore_open_host(bw_ctx* c, const uint8_t prk[32], const uint
     return BW_OK;
 }
 
+// ------------------------------------------------------------------ the shared steps
+RsLocator bw::rs_locator(const bw_restore* s) {
+    const uint32_t item_cap = s->n_items ? s->item_cap : 0, entry_cap = s->entries.empty() ? 0 : s->entry_cap;
+    return RsLocator{(const uint8_t*)s->items.p,  (const uint32_t*)s->item_tab.p,  (const uint32_t*)s->item_pos.p,
+                     (const bw_unpack_entry*)s->d_entries.p, (const uint32_t*)s->entry_tab.p, item_cap, entry_cap};
+}
+
+std::vector<PrPackfile> bw::rs_packfile_table(const bw_restore* s) {
+    std::vector<PrPackfile> t(s->pf.size());
+    for (size_t p = 0; p < t.size(); p++) t[p] = PrPackfile{s->pf[p].size, s->pf[p].header_len};
+    return t;
+}
+
+// scratch: [offsets, 8 m | nonces, 12 m]
+int bw::rs_fetch_nonces(bw_ctx* c, const uint8_t* d_pf, const uint64_t* n_off, uint64_t m, DevBuf& scratch, uint8_t* out) {
+    if (int rc = ensure(c, scratch, 20 * m + 16)) return rc;
+    uint8_t* b = P<uint8_t>(scratch);
+    if (m) {
+        HIPCHK(c, hipMemcpyAsync(b, n_off, 8 * m, hipMemcpyHostToDevice, c->stream));
+        launch_gather12(c->stream, d_pf, (const uint64_t*)b, m, b + 8 * m);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(out, b + 8 * m, 12 * m, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BW_OK;
+}
+
 // hashes (host, n x 32) -> entry index and status (host)
 static int rs_locate(bw_restore* s, const uint8_t* hashes, uint64_t n, uint64_t* idx, uint8_t* st) {
     bw_ctx* c = s->c;
@@ -438,9 +463,7 @@ static int rs_locate(bw_restore* s, const uint8_t* hashes, uint64_t n, uint64_t*
     uint8_t* d_h = P<uint8_t>(s->q) + 8 * n;
     uint8_t* d_st = d_h + 32 * n;
     HIPCHK(c, hipMemcpyAsync(d_h, hashes, 32 * n, hipMemcpyHostToDevice, c->stream));
-    launch_rs_locate(c->stream, d_h, n, P<uint8_t>(s->items), P<uint32_t>(s->item_tab), s->n_items ? s->item_cap : 0,
-                     P<uint32_t>(s->item_pos), P<bw_unpack_entry>(s->d_entries), P<uint32_t>(s->entry_tab),
-                     s->entries.empty() ? 0 : s->entry_cap, d_idx, d_st);
+    launch_rs_locate(c->stream, d_h, n, rs_locator(s), d_idx, d_st);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(idx, d_idx, 8 * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(st, d_st, n, hipMemcpyDeviceToHost, c->stream));
@@ -482,12 +505,197 @@ int bw::rs_decode(bw_restore* s, const std::vector<uint64_t>& eidx, const std::v
                              P<uint8_t>(s->slot_buf), off.data(), out_len.data(), st.data(), t.slot_len, t.map);
 }
 
+int bw::rs_tree_decode(bw_restore* s, const std::vector<uint64_t>& eidx, uint32_t flags, uint64_t ni, RsTables& t,
+                       std::vector<uint8_t>& bst) {
+    const uint64_t m = eidx.size();
+    std::vector<uint64_t> off(m), blen;
+    for (uint64_t k = 0; k < m; k++) off[k] = k * RS_SLOT_STRIDE;
+    if (int rc = rs_tables(s, m, ni, t)) return rc;
+    return rs_decode(s, eidx, off, flags, t, blen, bst);
+}
+
+int bw::rs_tree_parse(bw_restore* s, const RsTables& t, uint64_t m, std::vector<RsTreeHdr>* hd) {
+    bw_ctx* c = s->c;
+    if (int rc = ensure(c, s->q, m * sizeof(RsTreeHdr) + 16)) return rc;
+    launch_rs_tree_parse(c->stream, P<uint8_t>(s->slot_buf), t.slot_off, t.slot_len, m, P<RsTreeHdr>(s->q));
+    if (!hd) return BW_OK;
+    HIPCHK(c, hipGetLastError());
+    hd->resize(m);
+    HIPCHK(c, hipMemcpyAsync(hd->data(), s->q.p, m * sizeof(RsTreeHdr), hipMemcpyDeviceToHost, c->stream));
+    return BW_OK;
+}
+
 // ------------------------------------------------------------------ the tree walk
 namespace {
 struct TreeReq {
     std::array<uint8_t, 32> hash;
     uint64_t slot;  // which of the level's chains it continues
 };
+
+// The walk's state: the nodes found so far (node i's tree blob has hash node_hash[i]), their packed
+// names, the chunk rows of the File nodes, and the level being fetched.
+struct TreeWalk {
+    bw_restore* s;
+    uint32_t flags;
+    bw_restore_error* err;
+    std::vector<bw_restore_node> N;
+    std::vector<std::array<uint8_t, 32>> node_hash;
+    std::vector<uint8_t> nm, rows;
+    std::vector<uint64_t> level;             // nodes whose trees this level fetches, in node order
+    std::vector<std::vector<uint8_t>> kids;  // per node of the level: its chain's children rows, in chain order
+};
+
+// What one sub-batch's blobs hold: the parsed headers, and the names and children rows the emit
+// kernel packed.  The emit table has two regions per blob, its name and its rows, in three columns.
+struct TreeBatch {
+    std::vector<RsTreeHdr> hd;
+    std::vector<uint64_t> reg;  // src[2m] | len[2m] | dst[2m]
+    std::vector<uint8_t> pk;
+    uint64_t m = 0;
+    static uint64_t name(uint64_t k) { return 2 * k; }
+    static uint64_t rows(uint64_t k) { return 2 * k + 1; }
+    uint64_t* src() { return reg.data(); }
+    uint64_t* len() { return reg.data() + 2 * m; }
+    uint64_t* dst() { return reg.data() + 4 * m; }
+};
+
+int tw_fail(TreeWalk& w, const uint8_t* h, uint32_t reason, const char* why) {
+    memcpy(w.err->hash, h, 32);
+    w.err->reason = reason;
+    w.s->c->err = std::string("restore: tree blob refused: ") + why;
+    return BW_EFORMAT;
+}
+
+// m <= slots requests located, opened, decoded and parsed; names (a chain's first piece only) and
+// children rows packed by one kernel and brought back
+int tw_fetch(TreeWalk& w, const TreeReq* rq, uint64_t m, bool first_piece, TreeBatch& b) {
+    bw_restore* s = w.s;
+    bw_ctx* c = s->c;
+    std::vector<uint8_t> hs(32 * m), lst(m), bst;
+    std::vector<uint64_t> eidx(m);
+    for (uint64_t k = 0; k < m; k++) memcpy(&hs[32 * k], rq[k].hash.data(), 32);
+    if (int rc = rs_locate(s, hs.data(), m, eidx.data(), lst.data())) return rc;
+    for (uint64_t k = 0; k < m; k++) {
+        if (lst[k]) return tw_fail(w, &hs[32 * k], lst[k], "not found");
+        if (s->entries[eidx[k]].kind != BW_BLOB_TREE) return tw_fail(w, &hs[32 * k], BW_RESTORE_ENOTTREE, "not a tree");
+    }
+    RsTables t;
+    if (int rc = rs_tree_decode(s, eidx, w.flags, 5 * m, t, bst)) return rc;  // the instance part holds the emit table
+    for (uint64_t k = 0; k < m; k++)
+        if (bst[k]) return tw_fail(w, &hs[32 * k], bst[k], "failed to open or decode");
+    if (int rc = rs_tree_parse(s, t, m, &b.hd)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    b.m = m;
+    b.reg.assign(6 * m, 0);
+    uint64_t packed = 0;
+    for (uint64_t k = 0; k < m; k++) {
+        const RsTreeHdr& h = b.hd[k];
+        if (h.status) return tw_fail(w, &hs[32 * k], h.status, "bincode::deserialize::<Tree> fails");
+        // the parser bounded both regions by the blob (<= 3 MiB)
+        b.src()[b.name(k)] = k * RS_SLOT_STRIDE + h.name_pos;
+        b.len()[b.name(k)] = first_piece ? h.name_len : 0;
+        b.dst()[b.name(k)] = packed;
+        packed += b.len()[b.name(k)];
+        b.src()[b.rows(k)] = k * RS_SLOT_STRIDE + h.ch_pos;
+        b.len()[b.rows(k)] = 32 * h.n_children;
+        b.dst()[b.rows(k)] = packed;
+        packed += 32 * h.n_children;
+    }
+    b.pk.resize(packed);
+    if (!packed) return BW_OK;
+    if (int rc = ensure(c, s->emit, packed + 16)) return rc;
+    uint64_t* d_reg = t.dst_off;  // 6m of the 10m + 1 words behind the slot tables
+    HIPCHK(c, hipMemcpyAsync(d_reg, b.reg.data(), 48 * m, hipMemcpyHostToDevice, c->stream));
+    launch_rs_tree_emit(c->stream, P<uint8_t>(s->slot_buf), d_reg, d_reg + 2 * m, d_reg + 4 * m, 2 * m, P<uint8_t>(s->emit));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(b.pk.data(), s->emit.p, packed, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BW_OK;
+}
+
+// a sub-batch's blobs into the walk: a chain's first piece describes its node, every piece adds
+// children, and the next round follows every next_sibling
+void tw_append(TreeWalk& w, const TreeReq* rq, bool first_piece, TreeBatch& b, std::vector<TreeReq>& next) {
+    for (uint64_t k = 0; k < b.m; k++) {
+        const RsTreeHdr& h = b.hd[k];
+        const uint64_t j = rq[k].slot;
+        if (first_piece) {
+            bw_restore_node& nd = w.N[w.level[j]];
+            nd.kind = h.kind;
+            nd.flags = h.flags;
+            nd.size = h.size;
+            nd.mtime = h.mtime;
+            nd.ctime = h.ctime;
+            nd.name_off = w.nm.size();
+            nd.name_len = h.name_len;
+            const uint8_t* n0 = b.pk.data() + b.dst()[b.name(k)];
+            w.nm.insert(w.nm.end(), n0, n0 + h.name_len);
+        }
+        const uint8_t* r0 = b.pk.data() + b.dst()[b.rows(k)];
+        w.kids[j].insert(w.kids[j].end(), r0, r0 + 32 * h.n_children);
+        if (h.has_next) {
+            TreeReq rq_next;
+            memcpy(rq_next.hash.data(), h.next, 32);
+            rq_next.slot = j;
+            next.push_back(rq_next);
+        }
+    }
+}
+
+// one level: round r fetches piece r of every sibling chain that has one, `slots` blobs at a time
+int tw_level(TreeWalk& w) {
+    const uint64_t slots = w.s->slots, max_pieces = w.s->entries.size();
+    w.kids.assign(w.level.size(), std::vector<uint8_t>());
+    std::vector<TreeReq> cur(w.level.size()), next;
+    for (uint64_t j = 0; j < w.level.size(); j++) cur[j] = TreeReq{w.node_hash[w.level[j]], j};
+    TreeBatch b;
+    for (uint64_t round = 0; !cur.empty(); round++) {
+        if (round > max_pieces) return tw_fail(w, cur[0].hash.data(), BW_RESTORE_EFORMAT, "a sibling chain longer than the store");
+        next.clear();
+        for (uint64_t lo = 0; lo < cur.size(); lo += slots) {
+            const uint64_t m = std::min<uint64_t>(slots, cur.size() - lo);
+            if (int rc = tw_fetch(w, &cur[lo], m, round == 0, b)) return rc;
+            tw_append(w, &cur[lo], round == 0, b, next);
+        }
+        cur.swap(next);
+    }
+    return BW_OK;
+}
+
+// the next level: the children of every Dir node, parents in node order; a File node's rows are its chunks
+int tw_close_level(TreeWalk& w) {
+    const uint64_t hard_cap = 1ull << 32;  // a walk that grows past this is reported as it stands
+    std::vector<uint64_t> nl;
+    for (uint64_t j = 0; j < w.level.size(); j++) {
+        const uint64_t p = w.level[j], nch = w.kids[j].size() / 32;
+        w.N[p].n_children = nch;
+        if (w.N[p].kind == BW_TREE_FILE) {
+            w.N[p].child_first = w.rows.size() / 32;
+            w.rows.insert(w.rows.end(), w.kids[j].begin(), w.kids[j].end());
+            continue;
+        }
+        w.N[p].child_first = w.N.size();
+        for (uint64_t k = 0; k < nch; k++) {
+            std::array<uint8_t, 32> h;
+            memcpy(h.data(), &w.kids[j][32 * k], 32);
+            // a tree that is its own ancestor never ends (the reference's queue never drains)
+            for (uint64_t a = p; a != ~0ull; a = w.N[a].parent)
+                if (w.node_hash[a] == h) return tw_fail(w, h.data(), BW_RESTORE_EFORMAT, "a directory that contains itself");
+            bw_restore_node nd;
+            memset(&nd, 0, sizeof(nd));
+            nd.parent = p;
+            nl.push_back(w.N.size());
+            w.N.push_back(nd);
+            w.node_hash.push_back(h);
+        }
+        if (w.N.size() > hard_cap || w.rows.size() / 32 > hard_cap) {
+            nl.clear();
+            break;
+        }
+    }
+    w.level.swap(nl);
+    return BW_OK;
+}
 }  // namespace
 
 extern "C" int bw_restore_trees(bw_restore* s, const uint8_t root_hash[32], uint32_t flags, bw_restore_node* nodes,
@@ -495,152 +703,30 @@ extern "C" int bw_restore_trees(bw_restore* s, const uint8_t root_hash[32], uint
                                 uint64_t chunks_cap, bw_restore_counts* counts, bw_restore_error* err) {
     if (!s || !root_hash || !counts || !err || (flags & ~BW_UNPACK_VERIFY)) return BW_EINVAL;
     if ((node_cap && !nodes) || (names_cap && !names) || (chunks_cap && !chunks)) return BW_EINVAL;
-    bw_ctx* c = s->c;
-    hipSetDevice(c->device);
+    hipSetDevice(s->c->device);
     memset(counts, 0, sizeof(*counts));
     memset(err, 0, sizeof(*err));
-    auto fail = [&](const uint8_t* h, uint32_t reason, const char* why) {
-        memcpy(err->hash, h, 32);
-        err->reason = reason;
-        c->err = std::string("restore: tree blob refused: ") + why;
-        return BW_EFORMAT;
-    };
-    std::vector<bw_restore_node> N(1);
-    std::vector<std::array<uint8_t, 32>> node_hash(1);
-    std::vector<uint8_t> nm, rows;
-    memset(&N[0], 0, sizeof(N[0]));
-    N[0].parent = ~0ull;
-    memcpy(node_hash[0].data(), root_hash, 32);
-    std::vector<uint64_t> level{0};  // nodes whose trees this level fetches, in node order
-    const uint64_t max_pieces = s->entries.size();
-    const uint64_t hard_cap = 1ull << 32;  // a walk that grows past this is reported as it stands
-
-    while (!level.empty()) {
-        std::vector<std::vector<uint8_t>> kids(level.size());
-        std::vector<TreeReq> cur(level.size()), next;
-        for (uint64_t j = 0; j < level.size(); j++) cur[j] = TreeReq{node_hash[level[j]], j};
-        for (uint64_t round = 0; !cur.empty(); round++) {
-            if (round > max_pieces) return fail(cur[0].hash.data(), BW_RESTORE_EFORMAT, "a sibling chain longer than the store");
-            next.clear();
-            for (uint64_t lo = 0; lo < cur.size(); lo += s->slots) {
-                const uint64_t m = std::min<uint64_t>(s->slots, cur.size() - lo);
-                // 1. locate
-                std::vector<uint8_t> hs(32 * m), lst(m);
-                std::vector<uint64_t> eidx(m), off(m);
-                for (uint64_t k = 0; k < m; k++) memcpy(&hs[32 * k], cur[lo + k].hash.data(), 32);
-                if (int rc = rs_locate(s, hs.data(), m, eidx.data(), lst.data())) return rc;
-                for (uint64_t k = 0; k < m; k++) {
-                    if (lst[k]) return fail(&hs[32 * k], lst[k], "not found");
-                    if (s->entries[eidx[k]].kind != BW_BLOB_TREE) return fail(&hs[32 * k], BW_RESTORE_ENOTTREE, "not a tree");
-                    off[k] = k * RS_SLOT_STRIDE;
-                }
-                // 2. open and decode
-                RsTables t;
-                if (int rc = rs_tables(s, m, 5 * m, t)) return rc;  // the instance part holds the emit tables
-                std::vector<uint64_t> blen;
-                std::vector<uint8_t> bst;
-                if (int rc = rs_decode(s, eidx, off, flags, t, blen, bst)) return rc;
-                for (uint64_t k = 0; k < m; k++)
-                    if (bst[k]) return fail(&hs[32 * k], bst[k], "failed to open or decode");
-                // 3. parse
-                if (int rc = ensure(c, s->q, m * sizeof(RsTreeHdr) + 16)) return rc;
-                launch_rs_tree_parse(c->stream, P<uint8_t>(s->slot_buf), t.slot_off, t.slot_len, m, P<RsTreeHdr>(s->q));
-                HIPCHK(c, hipGetLastError());
-                std::vector<RsTreeHdr> hd(m);
-                HIPCHK(c, hipMemcpyAsync(hd.data(), s->q.p, m * sizeof(RsTreeHdr), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                // names (a chain's first piece only) and children rows, packed by one kernel
-                std::vector<uint64_t> reg(6 * m);  // src[2m] | len[2m] | dst[2m]
-                uint64_t packed = 0;
-                for (uint64_t k = 0; k < m; k++) {
-                    if (hd[k].status) return fail(&hs[32 * k], hd[k].status, "bincode::deserialize::<Tree> fails");
-                    // the parser bounded both regions by the blob (<= 3 MiB)
-                    reg[2 * k] = off[k] + hd[k].name_pos;
-                    reg[2 * m + 2 * k] = round == 0 ? hd[k].name_len : 0;
-                    reg[4 * m + 2 * k] = packed;
-                    packed += reg[2 * m + 2 * k];
-                    reg[2 * k + 1] = off[k] + hd[k].ch_pos;
-                    reg[2 * m + 2 * k + 1] = 32 * hd[k].n_children;
-                    reg[4 * m + 2 * k + 1] = packed;
-                    packed += 32 * hd[k].n_children;
-                }
-                std::vector<uint8_t> pk(packed);
-                if (packed) {
-                    if (int rc = ensure(c, s->emit, packed + 16)) return rc;
-                    uint64_t* d_reg = t.dst_off;  // 6m of the 10m + 1 words behind the slot tables
-                    HIPCHK(c, hipMemcpyAsync(d_reg, reg.data(), 48 * m, hipMemcpyHostToDevice, c->stream));
-                    launch_rs_tree_emit(c->stream, P<uint8_t>(s->slot_buf), d_reg, d_reg + 2 * m, d_reg + 4 * m, 2 * m,
-                                        P<uint8_t>(s->emit));
-                    HIPCHK(c, hipGetLastError());
-                    HIPCHK(c, hipMemcpyAsync(pk.data(), s->emit.p, packed, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                }
-                for (uint64_t k = 0; k < m; k++) {
-                    const uint64_t j = cur[lo + k].slot;
-                    if (round == 0) {
-                        bw_restore_node& nd = N[level[j]];
-                        nd.kind = hd[k].kind;
-                        nd.flags = hd[k].flags;
-                        nd.size = hd[k].size;
-                        nd.mtime = hd[k].mtime;
-                        nd.ctime = hd[k].ctime;
-                        nd.name_off = nm.size();
-                        nd.name_len = hd[k].name_len;
-                        nm.insert(nm.end(), pk.begin() + reg[4 * m + 2 * k], pk.begin() + reg[4 * m + 2 * k] + hd[k].name_len);
-                    }
-                    // 5. a chain's children in chain order
-                    const uint8_t* r0 = pk.data() + reg[4 * m + 2 * k + 1];
-                    kids[j].insert(kids[j].end(), r0, r0 + 32 * hd[k].n_children);
-                    // 4. the next round follows every next_sibling
-                    if (hd[k].has_next) {
-                        TreeReq rq;
-                        memcpy(rq.hash.data(), hd[k].next, 32);
-                        rq.slot = j;
-                        next.push_back(rq);
-                    }
-                }
-            }
-            cur.swap(next);
-        }
-        // 6. the next level: the children of every Dir node, parents in node order
-        std::vector<uint64_t> nl;
-        for (uint64_t j = 0; j < level.size(); j++) {
-            const uint64_t p = level[j];
-            const uint64_t nch = kids[j].size() / 32;
-            N[p].n_children = nch;
-            if (N[p].kind == BW_TREE_FILE) {
-                N[p].child_first = rows.size() / 32;
-                rows.insert(rows.end(), kids[j].begin(), kids[j].end());
-                continue;
-            }
-            N[p].child_first = N.size();
-            for (uint64_t k = 0; k < nch; k++) {
-                std::array<uint8_t, 32> h;
-                memcpy(h.data(), &kids[j][32 * k], 32);
-                // a tree that is its own ancestor never ends (the reference's queue never drains)
-                for (uint64_t a = p; a != ~0ull; a = N[a].parent)
-                    if (node_hash[a] == h) return fail(h.data(), BW_RESTORE_EFORMAT, "a directory that contains itself");
-                bw_restore_node nd;
-                memset(&nd, 0, sizeof(nd));
-                nd.parent = p;
-                nl.push_back(N.size());
-                N.push_back(nd);
-                node_hash.push_back(h);
-            }
-            if (N.size() > hard_cap || rows.size() / 32 > hard_cap) {
-                nl.clear();
-                break;
-            }
-        }
-        level.swap(nl);
+    TreeWalk w;
+    w.s = s;
+    w.flags = flags;
+    w.err = err;
+    w.N.resize(1);
+    w.node_hash.resize(1);
+    memset(&w.N[0], 0, sizeof(w.N[0]));
+    w.N[0].parent = ~0ull;
+    memcpy(w.node_hash[0].data(), root_hash, 32);
+    w.level.assign(1, 0);
+    while (!w.level.empty()) {
+        if (int rc = tw_level(w)) return rc;
+        if (int rc = tw_close_level(w)) return rc;
     }
-    counts->n_nodes = N.size();
-    counts->name_bytes = nm.size();
-    counts->n_chunks = rows.size() / 32;
-    if (N.size() > node_cap || nm.size() > names_cap || rows.size() / 32 > chunks_cap) return BW_ENOSPC;
-    memcpy(nodes, N.data(), N.size() * sizeof(bw_restore_node));
-    if (!nm.empty()) memcpy(names, nm.data(), nm.size());
-    if (!rows.empty()) memcpy(chunks, rows.data(), rows.size());
+    counts->n_nodes = w.N.size();
+    counts->name_bytes = w.nm.size();
+    counts->n_chunks = w.rows.size() / 32;
+    if (w.N.size() > node_cap || w.nm.size() > names_cap || w.rows.size() / 32 > chunks_cap) return BW_ENOSPC;
+    memcpy(nodes, w.N.data(), w.N.size() * sizeof(bw_restore_node));
+    if (!w.nm.empty()) memcpy(names, w.nm.data(), w.nm.size());
+    if (!w.rows.empty()) memcpy(chunks, w.rows.data(), w.rows.size());
     return BW_OK;
 }
 
