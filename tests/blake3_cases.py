@@ -8,7 +8,10 @@ every length 0..130 (each byte position of the first two blocks), and every posi
 (1, 2, 32, 33, 34 and 64 leaves), each at four source alignments mod 16.
 
 TREE: the batch path alone (k_b3_lines / k_b3_upper): the official test-vector lengths and the leaf
-counts around the lane-per-blob / wave-per-blob switch and the upper tree's passes, up to 3 MiB + 1.
+counts around 64 leaves and around the upper tree's passes, up to 3 MiB + 1.  In a batch of these
+cases alone (a few hundred blobs) k_b3_upper gives every blob a 4-wave workgroup; its other path,
+a lane per blob of up to 64 leaves and a wave per larger one from a bound of 8193 blobs on, sees
+them in the batches of tests/blake3_many_cases.py.
 """
 from backuwup_amd.synth import splitmix_bytes
 

@@ -64,8 +64,10 @@ def test_blake3_lengths(b3ctx, oracle):
 
 def test_blake3_tree_shapes_batched(b3ctx, oracle):
     ctx = b3ctx
-    # every leaf count around the group (4 leaves), lane-per-blob (<= 64 leaves) and wave-per-blob
-    # tree paths, ragged and exact, hashed in one batch
+    # every leaf count around the group (4 leaves) and around 64 leaves, ragged and exact, hashed in
+    # one batch.  At 417 blobs (a bound of at most B3_UPPER_BLOCK_BLOBS) k_b3_upper gives every blob
+    # above one group a 4-wave workgroup; the lane-per-blob and wave-per-blob paths of larger batches
+    # see these leaf counts in tests/test_gpu_blake3_many_blobs.py
     lens = [k * 1024 + d for k in range(1, 140) for d in (-1, 0, 1)]
     data = splitmix_bytes(17, sum(lens) + 64)
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) + 3
@@ -77,9 +79,12 @@ def test_blake3_tree_shapes_batched(b3ctx, oracle):
 
 def test_blake3_upper_tree_levels(b3ctx, oracle):
     ctx = b3ctx
-    # wave-per-blob upper tree: leaf counts around its global passes (more than 64 level-2 nodes,
-    # i.e. > 259 leaves) and the register levels below them, every spine-bit pattern near powers
-    # of two, next to lane-per-blob blobs in the same launch
+    # the upper tree of a large blob: leaf counts around its passes through global memory (more than
+    # 64 level-2 nodes, i.e. > 259 leaves) and the register levels below them, every spine-bit
+    # pattern near powers of two, next to blobs of up to 64 leaves in the same launch.  At 114 blobs
+    # every one of them is built by a 4-wave workgroup (b3_upper_wave<false, 256>); the wave-per-blob
+    # and lane-per-blob paths of batches above B3_UPPER_BLOCK_BLOBS blobs are pinned in
+    # tests/test_gpu_blake3_many_blobs.py
     leaves = [65, 66, 67, 68, 127, 128, 129, 255, 256, 257, 258, 259, 260, 261, 263, 264, 511, 512, 513, 515,
               516, 517, 1000, 1023, 1024, 1025, 2047, 2048, 2049, 3071, 3072, 4095, 4096, 4097, 5000, 8191, 8193]
     lens = [k * 1024 + d for k in leaves for d in (-1, 0, 1)] + [5 * 1024, 64 * 1024 + 7, 9000]
