@@ -124,6 +124,27 @@ class BwPruneError(ctypes.Structure):
                 ("reason", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+BW_DIFF_ADDED, BW_DIFF_REMOVED, BW_DIFF_MODIFIED, BW_DIFF_TYPE_CHANGED = 1, 2, 3, 4
+BW_DIFF_UNREADABLE, BW_DIFF_TRUNCATED = 1, 2
+
+
+class BwDiffSide(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("size", ctypes.c_uint64), ("mtime", ctypes.c_uint64), ("ctime", ctypes.c_uint64),
+                ("n_children", ctypes.c_uint64)]
+
+
+class BwDiffRecord(ctypes.Structure):
+    _fields_ = [("change", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("parent", ctypes.c_uint64),
+                ("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint64), ("a", BwDiffSide), ("b", BwDiffSide),
+                ("common_prefix", ctypes.c_uint64), ("common_suffix", ctypes.c_uint64), ("n_new", ctypes.c_uint64)]
+
+
+class BwDiffCounts(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_uint64), ("name_bytes", ctypes.c_uint64), ("n_read", ctypes.c_uint64),
+                ("n_levels", ctypes.c_uint64), ("n_errors", ctypes.c_uint64)]
+
+
 BW_CHECK_E_RANGE, BW_CHECK_E_ORDER, BW_CHECK_E_UNINDEXED, BW_CHECK_E_SHADOWED = 1, 2, 4, 8
 BW_CHECK_SKIPPED, BW_CHECK_IDUPLICATE = 32, 33
 BW_CHECK_AUTH, BW_CHECK_FULL = 1, 2
@@ -285,6 +306,9 @@ SIGNATURES = [
     ("bw_prune_repack_device", ctypes.c_int, [vp, u64p, ctypes.c_uint64, ctypes.POINTER(BwPackfile), ctypes.c_uint64, vp,
                                               vp]),
     ("bw_prune_repack", ctypes.c_int, [vp, u64p, ctypes.c_uint64, ctypes.POINTER(BwPackfile), ctypes.c_uint64, vp, vp]),
+    ("bw_diff_trees", ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(BwDiffRecord), ctypes.c_uint64, vp,
+                                     ctypes.c_uint64, u8p, ctypes.POINTER(BwDiffCounts), ctypes.POINTER(BwPruneError),
+                                     ctypes.c_uint64]),
     ("bw_auth_device", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_auth", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_check_structure", ctypes.c_int, [vp, u8p, u8p, ctypes.POINTER(BwCheckPackfileStat),

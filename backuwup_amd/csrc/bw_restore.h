@@ -256,4 +256,7 @@ struct bw_restore {
     DevBuf pr_bits, pr_front[2], pr_ctr, pr_err, pr_stat, pr_tab, pr_hdr;  // prune (bw_prune.hip)
     DevBuf ck_buf;  // check (bw_check.hip)
     DevBuf rk_buf;  // rekey (bw_rekey.hip)
+    // diff (bw_diff.hip): a level's nodes and references (this level, the next), chain rounds, tables and arenas
+    DevBuf df_nodes[2], df_refs[2], df_chain[2], df_out, df_take, df_stage, df_seghash, df_lvl, df_rows, df_rowseg;
+    DevBuf df_tab, df_rtab, df_rec, df_names, df_err, df_read, df_ctr;
 };

@@ -1,5 +1,9 @@
-"""Diff by listings: what changed between two snapshots of one store, from two full tree walks.  The
-reference has no diff.
+"""Diff: what changed between two snapshots of one store.  The reference has no diff.
+
+Two forms.  trees() / diff() are the device walk (bw_diff_trees): it opens only the tree blobs on a
+changed path, carries on past damage (errors are collected, flags mark unreadable and truncated
+sides) and sees how a next_sibling chain was split, as the hashes do.  listing_changes() /
+full_walk_diff() are the walk-everything form, from two full tree walks.
 
 A Tree blob holds its own name, kind and metadata and names its children by hash
 (filesystem/mod.rs:63-77), so two subtrees are equal exactly when their listings are.
@@ -11,22 +15,34 @@ full_walk_diff() is the whole answer over a store held as lists of bytes: the tw
 comparison, and with sizes=True what each snapshot alone keeps alive in the store (two prune.mark
 calls).
 
-This is the walk-everything form: both roots are read in full, however little changed, a tree blob
-that cannot be read ends the call as it ends a restore (restore.TreeError), and a listing does not
-show how a next_sibling chain was split, so two chains with the same children are equal here.  The
-names trees() and diff() are left free for a walk that opens only the tree blobs on changed paths."""
+In the walk-everything form both roots are read in full, however little changed, a tree blob that
+cannot be read ends the call as it ends a restore (restore.TreeError), and a listing does not show
+how a next_sibling chain was split, so two chains with the same children are equal there."""
+import ctypes
 import hashlib
 import struct
 
 import numpy as np
 
 from . import _lib, prune
+from ._lib import check
 from .context import UNPACK_ENTRY_DTYPE
+from .prune import ERROR_DTYPE
 from .restore import Session
 
 ADDED, REMOVED, MODIFIED, TYPE_CHANGED = 1, 2, 3, 4
 CHANGES = {ADDED: "added", REMOVED: "removed", MODIFIED: "modified", TYPE_CHANGED: "type_changed"}
 SIDE_FIELDS = ("kind", "flags", "size", "mtime", "ctime", "n_children")
+F_UNREADABLE, F_TRUNCATED = _lib.BW_DIFF_UNREADABLE, _lib.BW_DIFF_TRUNCATED
+NONE = 2**64 - 1
+SIDE_DTYPE = np.dtype([("hash", "u1", (32,)), ("kind", "<u4"), ("flags", "<u4"), ("size", "<u8"), ("mtime", "<u8"),
+                       ("ctime", "<u8"), ("n_children", "<u8")])
+RECORD_DTYPE = np.dtype([("change", "<u4"), ("flags", "<u4"), ("parent", "<u8"), ("name_off", "<u8"), ("name_len", "<u8"),
+                         ("a", SIDE_DTYPE), ("b", SIDE_DTYPE), ("common_prefix", "<u8"), ("common_suffix", "<u8"),
+                         ("n_new", "<u8")])
+assert SIDE_DTYPE.itemsize == ctypes.sizeof(_lib.BwDiffSide) == 72
+assert RECORD_DTYPE.itemsize == ctypes.sizeof(_lib.BwDiffRecord) == 200
+COUNT_FIELDS = [f for f, _ in _lib.BwDiffCounts._fields_]
 
 
 class _Listing:
@@ -166,3 +182,75 @@ def full_walk_diff(ctx, packfiles, ids, entries, index_items, prk, root_a, root_
     only_a, only_b = live_a & ~live_b, live_b & ~live_a
     return ch, dict(only_a_blobs=int(only_a.sum()), only_a_bytes=int(sealed[only_a].sum()),
                     only_b_blobs=int(only_b.sum()), only_b_bytes=int(sealed[only_b].sum()))
+
+
+# ------------------------------------------------------------------ the device walk
+def trees(session, root_a, root_b, verify=False):
+    """bw_diff_trees over an open restore Session: (records RECORD_DTYPE, names bytes, read u8 per
+    entry, counts dict, errors prune.ERROR_DTYPE).  A root may be None: an empty snapshot.  The buffers
+    grow until the walk fits them."""
+    roots = [None if r is None else (ctypes.c_uint8 * 32).from_buffer_copy(bytes(r)) for r in (root_a, root_b)]
+    read = np.zeros(max(session.n_entries, 1), dtype=np.uint8)
+    cnt = _lib.BwDiffCounts()
+    caps = [1024, 1 << 16, 64]
+    while True:
+        records = np.zeros(caps[0], dtype=RECORD_DTYPE)
+        names = np.zeros(caps[1], dtype=np.uint8)
+        errs = np.zeros(caps[2], dtype=ERROR_DTYPE)
+        rc = session._L.bw_diff_trees(session.h, roots[0], roots[1], _lib.BW_UNPACK_VERIFY if verify else 0,
+                                      records.ctypes.data_as(ctypes.POINTER(_lib.BwDiffRecord)), caps[0],
+                                      names.ctypes.data_as(ctypes.c_void_p), caps[1], read.ctypes.data_as(_lib.u8p),
+                                      ctypes.byref(cnt), errs.ctypes.data_as(ctypes.POINTER(_lib.BwPruneError)), caps[2])
+        if rc != _lib.BW_ENOSPC:
+            check(rc, session._ctx.h)
+            break
+        # the counts are the totals up to the level that did not fit: at least that, and twice the room
+        caps = [max(2 * cap, int(n)) if n > cap else cap
+                for cap, n in zip(caps, (cnt.n_records, cnt.name_bytes, cnt.n_errors))]
+    counts = {f: int(getattr(cnt, f)) for f in COUNT_FIELDS}
+    return (records[:counts["n_records"]], names[:counts["name_bytes"]].tobytes(), read[:session.n_entries], counts,
+            errs[:counts["n_errors"]])
+
+
+def record_changes(records, names):
+    """The records of trees() as dicts in listing_changes' shape, plus flags and both hashes: [dict(path,
+    change, flags, a, b, hash_a, hash_b, common_prefix, common_suffix, n_new)] sorted by path.  The path
+    is joined through parent (a parent's record comes first); the root's path is ''.  An unreadable
+    node has no name: its path ends in '?' and its hash in hex."""
+    names = bytes(names)
+    cols = {f: records[f].tolist() for f in ("change", "flags", "parent", "name_off", "name_len", "common_prefix",
+                                              "common_suffix", "n_new")}
+    sides = {x: list(zip(*[records[x][f].tolist() for f in SIDE_FIELDS])) if len(records) else [] for x in ("a", "b")}
+    hashes = {x: [bytes(h) for h in records[x]["hash"]] for x in ("a", "b")}
+    paths, out = [], []
+    for i in range(len(records)):
+        change, flags, parent = cols["change"][i], cols["flags"][i], cols["parent"][i]
+        if flags & F_UNREADABLE:
+            name = "?" + hashes["a" if change == REMOVED else "b"][i].hex()
+        else:
+            name = names[cols["name_off"][i]:cols["name_off"][i] + cols["name_len"][i]].decode("utf-8", "surrogateescape")
+        if parent == NONE:
+            path = ""
+        else:
+            path = paths[parent] + "/" + name if paths[parent] else name
+        paths.append(path)
+        out.append(dict(path=path, change=change, flags=flags,
+                        a=None if change == ADDED else dict(zip(SIDE_FIELDS, sides["a"][i])),
+                        b=None if change == REMOVED else dict(zip(SIDE_FIELDS, sides["b"][i])),
+                        hash_a=None if change == ADDED else hashes["a"][i],
+                        hash_b=None if change == REMOVED else hashes["b"][i],
+                        common_prefix=cols["common_prefix"][i], common_suffix=cols["common_suffix"][i],
+                        n_new=cols["n_new"][i]))
+    out.sort(key=lambda r: (r["path"], r["change"]))
+    return out
+
+
+def diff(ctx, packfiles, ids, entries, index_items, prk, root_a, root_b, verify=False, slots=0):
+    """What changed from snapshot root_a to snapshot root_b of one store (the arguments of
+    full_walk_diff), by the device walk: (changes, errors, counts).  changes = record_changes() of the
+    walk; errors = prune.ERROR_DTYPE records, which never end the call."""
+    packfiles = [bytes(b) for b in packfiles]
+    en = np.ascontiguousarray(entries, dtype=UNPACK_ENTRY_DTYPE)
+    with Session(ctx, prk, packfiles, ids, en, index_items, slots=slots) as s:
+        records, names, _, counts, errors = trees(s, root_a, root_b, verify=verify)
+    return record_changes(records, names), errors, counts

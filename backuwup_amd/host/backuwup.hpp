@@ -643,6 +643,67 @@ private:
     const std::vector<bw_unpack_entry>& entries_;
 };
 
+// ------------------------------------------------------------------ diff (no counterpart in the reference)
+// Over an open Restore: trees() = what changed from root a to root b (nullptr: an empty snapshot), by
+// the walk that opens only the tree blobs on changed paths.  Errors are collected and never end the call.
+class Diff {
+public:
+    struct Result {
+        std::vector<bw_diff_record> records;  // a parent before its children
+        std::vector<uint8_t> names;
+        std::vector<uint8_t> read;            // one byte per header entry: the tree blobs opened
+        bw_diff_counts counts{};
+        std::vector<bw_prune_error> errors;   // in no particular order
+
+        std::string name(size_t i) const {
+            const bw_diff_record& r = records[i];
+            return std::string(names.begin() + r.name_off, names.begin() + r.name_off + r.name_len);
+        }
+        // the names joined through parent; the root's path is empty
+        std::string path(size_t i) const {
+            const bw_diff_record& r = records[i];
+            if (r.parent == ~0ull) return "";
+            const std::string up = path(r.parent);
+            return up.empty() ? name(i) : up + "/" + name(i);
+        }
+    };
+
+    Diff(Context& ctx, Restore& session, const std::vector<bw_unpack_entry>& entries)
+        : ctx_(ctx), s_(session), entries_(entries) {}
+
+    Result trees(const BlobHash* a, const BlobHash* b, bool verify = false) {
+        Result d;
+        d.read.resize(entries_.size() + 1);
+        uint64_t rcap = 1024, ncap = 1 << 16, ecap = 64;
+        for (;;) {
+            d.records.resize(rcap + 1);
+            d.names.resize(ncap + 1);
+            d.errors.resize(ecap + 1);
+            const int rc = bw_diff_trees(s_.get(), a ? a->data() : nullptr, b ? b->data() : nullptr, verify ? BW_UNPACK_VERIFY : 0,
+                                         d.records.data(), rcap, d.names.data(), ncap, d.read.data(), &d.counts,
+                                         d.errors.data(), ecap);
+            if (rc != BW_ENOSPC) {
+                check(rc, ctx_.get());
+                break;
+            }
+            // the counts are the totals up to the level that did not fit
+            if (d.counts.n_records > rcap) rcap = std::max<uint64_t>(2 * rcap, d.counts.n_records);
+            if (d.counts.name_bytes > ncap) ncap = std::max<uint64_t>(2 * ncap, d.counts.name_bytes);
+            if (d.counts.n_errors > ecap) ecap = d.counts.n_errors;
+        }
+        d.records.resize(d.counts.n_records);
+        d.names.resize(d.counts.name_bytes);
+        d.errors.resize(d.counts.n_errors);
+        d.read.resize(entries_.size());
+        return d;
+    }
+
+private:
+    Context& ctx_;
+    Restore& s_;
+    const std::vector<bw_unpack_entry>& entries_;
+};
+
 // ------------------------------------------------------------------ check (no counterpart in the reference)
 // Over an open Restore: structure() = headers against index items and the layout of every blob
 // section, data() = every selected entry's bytes (BW_CHECK_AUTH: tags only, BW_CHECK_FULL: the unpack

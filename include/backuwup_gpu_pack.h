@@ -463,6 +463,69 @@ int bw_prune_repack_device(bw_restore* session, const uint64_t* order, uint64_t 
 int bw_prune_repack(bw_restore* session, const uint64_t* order, uint64_t n_moved, const bw_packfile* plan,
                     uint64_t n_new, const uint8_t* new_ids, uint8_t* out);
 
+/* ---- diff: what changed between two snapshots, opening only the tree blobs on changed paths ----
+ * The reference has no diff.  A Tree blob holds its own name, kind and metadata and names its children
+ * and its next_sibling by hash (filesystem/mod.rs:63-77), so equal hashes mean equal subtrees.  An
+ * item is a pair (A hash or none, B hash or none); the walk starts with the root pair and goes down
+ * level by level over an open restore session. */
+enum { BW_DIFF_ADDED = 1, BW_DIFF_REMOVED = 2, BW_DIFF_MODIFIED = 3, BW_DIFF_TYPE_CHANGED = 4 };
+#define BW_DIFF_UNREADABLE 1u /* a side's first piece could not be read: that side has its hash only  */
+#define BW_DIFF_TRUNCATED 2u  /* a later piece of a side's chain could not be read: its list ends there */
+typedef struct bw_diff_side {
+    uint8_t hash[32];
+    uint32_t kind;  /* BW_TREE_FILE or BW_TREE_DIR */
+    uint32_t flags; /* BW_TREE_HAS_*               */
+    uint64_t size, mtime, ctime;
+    uint64_t n_children; /* the rows of its whole next_sibling chain */
+} bw_diff_side;
+typedef struct bw_diff_record {
+    uint32_t change; /* BW_DIFF_ADDED .. BW_DIFF_TYPE_CHANGED */
+    uint32_t flags;  /* BW_DIFF_UNREADABLE, BW_DIFF_TRUNCATED  */
+    uint64_t parent; /* the record of the item above, ~0 for a root item; always lower than the record's own index */
+    uint64_t name_off, name_len; /* into `names`: the B side's name, A's for REMOVED; empty for an unreadable node */
+    bw_diff_side a, b;           /* an absent side is all zero */
+    uint64_t common_prefix, common_suffix, n_new; /* BW_DIFF_MODIFIED: over the two children lists */
+} bw_diff_record;
+typedef struct bw_diff_counts {
+    uint64_t n_records, name_bytes;
+    uint64_t n_read;   /* entries opened: the ones of read[]                      */
+    uint64_t n_levels; /* levels of the walk that hold a record                   */
+    uint64_t n_errors; /* always the full number                                  */
+} bw_diff_counts;
+
+/* root_a / root_b: 32 bytes each (host), or NULL for an empty snapshot; both NULL or equal bytes: no
+ * record, no error, nothing read, n_levels = 0.  flags: BW_UNPACK_VERIFY or 0.  Synchronous.
+ *   Equal hashes give no record and are not opened.  Otherwise one record per item: one side present
+ * is ADDED or REMOVED; both of one kind MODIFIED; File against Dir TYPE_CHANGED, whose sides are
+ * expanded apart.  The roots pair whatever their names.  A side's list is the children rows of its
+ * next_sibling chain in chain order.  MODIFIED: common_prefix = the equal leading rows, common_suffix
+ * = the equal trailing rows capped at min(n_a, n_b) - common_prefix, n_new = the B rows whose hash is
+ * nowhere in A's list.  A File's rows are chunk hashes and are never opened.  A child of a Dir item
+ * is unmatched when its hash does not occur in the other side's list; every unmatched child's first
+ * piece is read; per side the unmatched child at the lowest position represents its name,
+ * representatives with byte-equal names pair, every other one is one-sided, and one-sided Dirs are
+ * expanded all the way down.  Every comparison of hashes and names runs on the device.
+ *   read[e] (host, one byte per session entry) = 1 exactly for the Tree entries opened: first pieces
+ * of unmatched children (and of the roots) and later chain pieces of expanded items.
+ *   Errors never stop the walk and use prune's record: hash = the hash referred to, parent = the
+ * piece that names it (zero for a root), child_pos = its position there (~0 for a next_sibling, 0 / 1
+ * for root A / B), reason = a locate status, BW_RESTORE_ENOTTREE, BW_UNPACK_ERANGE / _ETAG / _EZSTD /
+ * _EDIGEST, or BW_RESTORE_EFORMAT (the parser, a chain of more pieces than the store has entries, a
+ * child whose hash is one of its ancestors' on its side: its first piece is read for the name and its
+ * list counts as empty).  A first piece that cannot be read gives a one-sided record with
+ * BW_DIFF_UNREADABLE; a later piece that cannot be read ends the list and sets BW_DIFF_TRUNCATED.
+ * counts->n_errors > err_cap -> BW_ENOSPC with everything else filled; errs is in no particular order.
+ *   Capacity: the walk stops at the first level whose records or names do not fit and returns
+ * BW_ENOSPC with counts holding the totals up to and including that level; the levels before it are
+ * filled in, and nothing is written past a cap.  A parent's record comes before its children's; the
+ * order inside a level is free.
+ *   Hard limit: the walk indexes a level in 32 bits.  A level of more than 2^30 nodes, or whose lists
+ * hold more than 2^30 children rows (a forged chain that names itself can grow one that far), ends
+ * the call with BW_ENOMEM, as does a device allocation that fails; nothing is filled in then. */
+int bw_diff_trees(bw_restore* session, const uint8_t* root_a, const uint8_t* root_b, uint32_t flags,
+                  bw_diff_record* records, uint64_t record_cap, uint8_t* names, uint64_t names_cap, uint8_t* read,
+                  bw_diff_counts* counts, bw_prune_error* errs, uint64_t err_cap);
+
 /* ---- check: is this store sound, are these bytes still the bytes that were sealed ----
  * The reference never verifies what it has written; this goes past it as prune does.  Three layers,
  * all synchronous: bw_auth(_device) recomputes AES-GCM tags without decrypting, bw_check_structure

@@ -242,6 +242,43 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_diff_side {
+        pub hash: [u8; 32],
+        pub kind: u32,
+        pub flags: u32,
+        pub size: u64,
+        pub mtime: u64,
+        pub ctime: u64,
+        pub n_children: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_diff_record {
+        pub change: u32,
+        pub flags: u32,
+        pub parent: u64,
+        pub name_off: u64,
+        pub name_len: u64,
+        pub a: bw_diff_side,
+        pub b: bw_diff_side,
+        pub common_prefix: u64,
+        pub common_suffix: u64,
+        pub n_new: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_diff_counts {
+        pub n_records: u64,
+        pub name_bytes: u64,
+        pub n_read: u64,
+        pub n_levels: u64,
+        pub n_errors: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
     pub struct bw_check_packfile_stat {
         pub n_entries: u64,
         pub n_range: u64,
@@ -302,6 +339,12 @@ pub mod ffi {
     pub const BW_RESTORE_ENOPACKFILE: u8 = 18;
     pub const BW_RESTORE_ENOTTREE: u8 = 19;
     pub const BW_RESTORE_EFORMAT: u8 = 20;
+    pub const BW_DIFF_ADDED: u32 = 1;
+    pub const BW_DIFF_REMOVED: u32 = 2;
+    pub const BW_DIFF_MODIFIED: u32 = 3;
+    pub const BW_DIFF_TYPE_CHANGED: u32 = 4;
+    pub const BW_DIFF_UNREADABLE: u32 = 1;
+    pub const BW_DIFF_TRUNCATED: u32 = 2;
     pub const BW_RESTORE_SKEW_SLOTS: u32 = 0x100;
 
     /// `fn(user, send, recv, bytes_per_rank)`: deliver `send[r * b ..]` to rank r's `recv[my_rank * b ..]`.
@@ -508,6 +551,11 @@ pub mod ffi {
                                       plan: *const bw_packfile, n_new: u64, new_ids: *const u8, d_out: *mut u8) -> c_int;
         pub fn bw_prune_repack(session: *mut bw_restore, order: *const u64, n_moved: u64, plan: *const bw_packfile,
                                n_new: u64, new_ids: *const u8, out: *mut u8) -> c_int;
+
+        pub fn bw_diff_trees(session: *mut bw_restore, root_a: *const u8, root_b: *const u8, flags: u32,
+                             records: *mut bw_diff_record, record_cap: u64, names: *mut u8, names_cap: u64,
+                             read: *mut u8, counts: *mut bw_diff_counts, errs: *mut bw_prune_error,
+                             err_cap: u64) -> c_int;
 
         pub fn bw_auth_device(ctx: *mut bw_ctx, prk: *const u8, d_src: *const u8, src_off: *const u64,
                               src_len: *const u64, n: u64, info: *const u8, info_len: u32, nonces: *const u8,
