@@ -145,6 +145,18 @@ class BwDiffCounts(ctypes.Structure):
                 ("n_levels", ctypes.c_uint64), ("n_errors", ctypes.c_uint64)]
 
 
+BW_PARENT_NEW, BW_PARENT_UNCHANGED, BW_PARENT_CHANGED, BW_PARENT_RACY, BW_PARENT_DIR, BW_PARENT_TYPE_CHANGED = range(6)
+
+
+class BwParentResult(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("status", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class BwParentCounts(ctypes.Structure):
+    _fields_ = [("n_read", ctypes.c_uint64), ("n_levels", ctypes.c_uint64), ("n_errors", ctypes.c_uint64),
+                ("n_unchanged", ctypes.c_uint64), ("unchanged_bytes", ctypes.c_uint64)]
+
+
 BW_CHECK_E_RANGE, BW_CHECK_E_ORDER, BW_CHECK_E_UNINDEXED, BW_CHECK_E_SHADOWED = 1, 2, 4, 8
 BW_CHECK_SKIPPED, BW_CHECK_IDUPLICATE = 32, 33
 BW_CHECK_AUTH, BW_CHECK_FULL = 1, 2
@@ -309,6 +321,9 @@ SIGNATURES = [
     ("bw_diff_trees", ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(BwDiffRecord), ctypes.c_uint64, vp,
                                      ctypes.c_uint64, u8p, ctypes.POINTER(BwDiffCounts), ctypes.POINTER(BwPruneError),
                                      ctypes.c_uint64]),
+    ("bw_parent_match", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(BwRestoreNode), ctypes.c_uint64,
+                                       vp, ctypes.c_uint64, ctypes.POINTER(BwParentResult), u8p,
+                                       ctypes.POINTER(BwParentCounts), ctypes.POINTER(BwPruneError), ctypes.c_uint64]),
     ("bw_auth_device", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_auth", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_check_structure", ctypes.c_int, [vp, u8p, u8p, ctypes.POINTER(BwCheckPackfileStat),

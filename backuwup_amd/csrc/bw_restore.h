@@ -259,4 +259,5 @@ struct bw_restore {
     // diff (bw_diff.hip): a level's nodes and references (this level, the next), chain rounds, tables and arenas
     DevBuf df_nodes[2], df_refs[2], df_chain[2], df_out, df_take, df_stage, df_seghash, df_lvl, df_rows, df_rowseg;
     DevBuf df_tab, df_rtab, df_rec, df_names, df_err, df_read, df_ctr;
+    DevBuf pm[24];  // parent match (bw_parent.hip): its buffers by PM_B_*
 };

@@ -340,6 +340,7 @@ extern "C" int bw_restore_close(bw_restore* s) {
                       &s->df_stage, &s->df_seghash, &s->df_lvl, &s->df_rows, &s->df_rowseg, &s->df_tab, &s->df_rtab, &s->df_rec,
                       &s->df_names, &s->df_err, &s->df_read, &s->df_ctr})
         free_dev(*b);
+    for (DevBuf& b : s->pm) free_dev(b);
     delete s;
     return BW_OK;
 }

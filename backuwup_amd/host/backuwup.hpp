@@ -704,6 +704,60 @@ private:
     const std::vector<bw_unpack_entry>& entries_;
 };
 
+// ------------------------------------------------------------------ parent match (no counterpart in the reference)
+// Over an open Restore: match() = which nodes of a stat-only scan are the parent snapshot's as they
+// stand, so that a backup need not read them.  The scan has the layout of Restore::Walk (scan_of()
+// makes one from a walk); errors are collected and never end the call.
+class ParentMatch {
+public:
+    struct Result {
+        std::vector<bw_parent_result> results;  // one per scan node: BW_PARENT_* and the parent's child hash
+        std::vector<uint8_t> read;              // one byte per header entry: the tree blobs opened
+        bw_parent_counts counts{};
+        std::vector<bw_prune_error> errors;     // in no particular order
+    };
+
+    ParentMatch(Context& ctx, Restore& session, const std::vector<bw_unpack_entry>& entries)
+        : ctx_(ctx), s_(session), entries_(entries) {}
+
+    // a listing as a scan: the File nodes name no chunks
+    static Restore::Walk scan_of(Restore::Walk w) {
+        for (auto& n : w.nodes)
+            if (n.kind == BW_TREE_FILE) n.child_first = n.n_children = 0;
+        w.chunks.clear();
+        return w;
+    }
+
+    // parent_root nullptr: no parent, every node is BW_PARENT_NEW; trust_before ~0 trusts every mtime
+    Result match(const BlobHash* parent_root, const std::vector<bw_restore_node>& nodes, const std::vector<uint8_t>& names,
+                 uint64_t trust_before = ~0ull, bool verify = false) {
+        Result m;
+        m.results.resize(nodes.size() + 1);
+        m.read.resize(entries_.size() + 1);
+        uint64_t ecap = 64;
+        for (;;) {
+            m.errors.resize(ecap + 1);
+            const int rc = bw_parent_match(s_.get(), parent_root ? parent_root->data() : nullptr, trust_before,
+                                           verify ? BW_UNPACK_VERIFY : 0, nodes.data(), nodes.size(), names.data(), names.size(),
+                                           m.results.data(), m.read.data(), &m.counts, m.errors.data(), ecap);
+            if (rc != BW_ENOSPC) {
+                check(rc, ctx_.get());
+                break;
+            }
+            ecap = m.counts.n_errors;
+        }
+        m.results.resize(nodes.size());
+        m.read.resize(entries_.size());
+        m.errors.resize(m.counts.n_errors);
+        return m;
+    }
+
+private:
+    Context& ctx_;
+    Restore& s_;
+    const std::vector<bw_unpack_entry>& entries_;
+};
+
 // ------------------------------------------------------------------ check (no counterpart in the reference)
 // Over an open Restore: structure() = headers against index items and the layout of every blob
 // section, data() = every selected entry's bytes (BW_CHECK_AUTH: tags only, BW_CHECK_FULL: the unpack

@@ -526,6 +526,70 @@ int bw_diff_trees(bw_restore* session, const uint8_t* root_a, const uint8_t* roo
                   bw_diff_record* records, uint64_t record_cap, uint8_t* names, uint64_t names_cap, uint8_t* read,
                   bw_diff_counts* counts, bw_prune_error* errs, uint64_t err_cap);
 
+/* ---- parent match: which files a new backup need not read ----
+ * The reference reads, chunks and hashes every file on every run (dir_packer.rs:231-282) and lets dedup
+ * discard the result; this goes past it, as restic's parent snapshot and git's index do.  A Tree blob
+ * holds its own name, kind and metadata and names its children by hash (filesystem/mod.rs:63-77), so a
+ * File's tree blob in the parent snapshot is the new snapshot's as it stands when name, kind, size,
+ * mtime and ctime are equal and the chunk list is assumed equal: the parent's child hash is the new
+ * child hash, no file byte is read and no tree blob is rebuilt.  That assumption is the heuristic. */
+enum {
+    BW_PARENT_NEW = 0,          /* no readable child of that name under the matched parent Dir, or the node above is not DIR */
+    BW_PARENT_UNCHANGED = 1,    /* File against File, equal flags with HAS_SIZE and HAS_MTIME, equal size, mtime and (where
+                                   flagged) ctime, mtime < trust_before */
+    BW_PARENT_CHANGED = 2,      /* File against File, anything else */
+    BW_PARENT_RACY = 3,         /* would be UNCHANGED, but mtime >= trust_before */
+    BW_PARENT_DIR = 4,          /* Dir against Dir: descended */
+    BW_PARENT_TYPE_CHANGED = 5  /* File against Dir or Dir against File: nothing below is matched */
+};
+typedef struct bw_parent_result {
+    uint8_t hash[32]; /* the parent snapshot's child hash; zero for BW_PARENT_NEW */
+    uint32_t status;  /* BW_PARENT_* */
+    uint32_t pad;
+} bw_parent_result;
+typedef struct bw_parent_counts {
+    uint64_t n_read;          /* entries opened: the ones of read[]                         */
+    uint64_t n_levels;        /* levels of the walk that hold an item; level 0 is the roots */
+    uint64_t n_errors;        /* always the full number                                     */
+    uint64_t n_unchanged;     /* scan nodes that are BW_PARENT_UNCHANGED                    */
+    uint64_t unchanged_bytes; /* the sum of their sizes: what the backup will not read      */
+} bw_parent_counts;
+
+/* The scan (host) is what a stat-only directory walk yields, in the layout of a bw_restore_trees
+ * listing: node 0 is the root; a Dir's children are the nodes [child_first, child_first + n_children);
+ * a File has n_children = 0; name_off / name_len point into names; parent is not looked at.  A listing
+ * of bw_restore_trees is a valid scan once its File nodes' n_children are zeroed.  It is checked in
+ * O(n) before anything is read: kind in {File, Dir}, name ranges inside names, a File without
+ * children, a Dir's children after itself, inside the scan, and no node the child of two; otherwise
+ * BW_EINVAL, with read all zero.  parent_root: 32 bytes (host), or NULL: every node is NEW, nothing
+ * is read, n_levels = 0.  flags: BW_UNPACK_VERIFY or 0.  Synchronous.
+ *   The walk is level by level.  Level 0 is the item (scan node 0, parent_root); the roots pair whatever
+ * their names.  For an item (scan Dir, hash) the hash's whole next_sibling chain is read and its
+ * children rows concatenated in chain order; of every row the first piece only is read, for its name,
+ * kind and metadata (a File's later pieces are never opened); the readable rows of one item are keyed
+ * by their whole name bytes, the lowest position winning among equal names; every scan child of the
+ * Dir probes that table (scan children with equal names get one answer) and gets its status from the
+ * table above.  trust_before is there because mtimes are whole seconds: the caller passes the parent
+ * snapshot's start time, ~0 trusts every mtime.  A Dir against Dir pair is an item of the next level;
+ * parent children no scan node names are not descended, so nothing under a removed directory is read.
+ * Every comparison of hashes and names, the verdict and the sums run on the device.
+ *   results[i] (host, one per scan node); read[e] (host, one byte per session entry) = 1 exactly for
+ * the Tree entries opened.  Errors never stop the walk and use prune's record with the diff walk's
+ * meaning: hash = the hash referred to, parent = the piece that names it (zero for the root),
+ * child_pos = its position there (~0 for a next_sibling, 0 for the root), reason = a locate status,
+ * BW_RESTORE_ENOTTREE, BW_UNPACK_ERANGE / _ETAG / _EZSTD / _EDIGEST, or BW_RESTORE_EFORMAT (the
+ * parser, or a chain of more pieces than the store has entries).  A row whose first piece cannot be
+ * read takes no part in the join, so the scan node of its name is NEW; a later piece of an item's
+ * chain that cannot be read ends the list there; an unreadable root makes scan node 0 NEW.
+ * counts->n_errors > err_cap -> BW_ENOSPC with everything else filled; errs is in no particular order.
+ *   Hard limit: a level is indexed in 32 bits.  A scan of more than 2^30 nodes, or a level whose lists
+ * hold more than 2^30 rows, ends the call with BW_ENOMEM, as does a device allocation that fails;
+ * nothing but read (zeros) is filled in then. */
+int bw_parent_match(bw_restore* session, const uint8_t* parent_root, uint64_t trust_before, uint32_t flags,
+                    const bw_restore_node* nodes, uint64_t n_nodes, const uint8_t* names, uint64_t names_len,
+                    bw_parent_result* results, uint8_t* read, bw_parent_counts* counts, bw_prune_error* errs,
+                    uint64_t err_cap);
+
 /* ---- check: is this store sound, are these bytes still the bytes that were sealed ----
  * The reference never verifies what it has written; this goes past it as prune does.  Three layers,
  * all synchronous: bw_auth(_device) recomputes AES-GCM tags without decrypting, bw_check_structure

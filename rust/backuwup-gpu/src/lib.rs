@@ -277,6 +277,25 @@ pub mod ffi {
         pub n_errors: u64,
     }
 
+    /// One scan node's answer from `bw_parent_match`: BW_PARENT_* and the parent snapshot's child hash.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_parent_result {
+        pub hash: [u8; 32],
+        pub status: u32,
+        pub pad: u32,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_parent_counts {
+        pub n_read: u64,
+        pub n_levels: u64,
+        pub n_errors: u64,
+        pub n_unchanged: u64,
+        pub unchanged_bytes: u64,
+    }
+
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default)]
     pub struct bw_check_packfile_stat {
@@ -556,6 +575,11 @@ pub mod ffi {
                              records: *mut bw_diff_record, record_cap: u64, names: *mut u8, names_cap: u64,
                              read: *mut u8, counts: *mut bw_diff_counts, errs: *mut bw_prune_error,
                              err_cap: u64) -> c_int;
+
+        pub fn bw_parent_match(session: *mut bw_restore, parent_root: *const u8, trust_before: u64, flags: u32,
+                               nodes: *const bw_restore_node, n_nodes: u64, names: *const u8, names_len: u64,
+                               results: *mut bw_parent_result, read: *mut u8, counts: *mut bw_parent_counts,
+                               errs: *mut bw_prune_error, err_cap: u64) -> c_int;
 
         pub fn bw_auth_device(ctx: *mut bw_ctx, prk: *const u8, d_src: *const u8, src_off: *const u64,
                               src_len: *const u64, n: u64, info: *const u8, info_len: u32, nonces: *const u8,
