@@ -28,12 +28,13 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # side's C ABI (bw_capi_pack.hip, include/backuwup_gpu_pack.h) and the drop-ins' small-message
 # hashing (bw_b3_small.hip) are outside the digest too, as is the read side (bw_zstd_dec.hip and its headers, and
 # the restore session, bw_restore.hip, and prune and check over it, bw_prune.hip, bw_check.hip; parity,
-# bw_parity.hip; the store's host-only layout rules, bw_store_layout.h; the diff walk, bw_diff.hip; the parent match, bw_parent.hip)
+# bw_parity.hip; the store's host-only layout rules, bw_store_layout.h; the diff walk, bw_diff.hip; the parent match, bw_parent.hip;
+# the tree-chain fetch those two share, bw_walk.h and its host-only planner bw_walk_host.h)
 OFF_PATH = ("bw_zstd.hip", "bw_seal.hip", "bw_pack.hip", "bw_tree.hip", "bw_comm.hip", "bw_dropin.hip", "bw_stream.hip",
             "bw_capi_pack.hip", "bw_b3_small.hip", "bw_b3_small.h", "bw_zstd_dec.hip", "bw_zstd_dec_core.h",
             "bw_unpack.h", "bw_restore.hip", "bw_restore.h", "bw_prune.hip", "bw_prune.h", "bw_check.hip", "bw_check.h", "bw_seal.h",
             "bw_rekey.hip", "bw_parity.hip", "bw_store_layout.h", "bw_diff.hip", "bw_diff.h", "bw_diff_host.h",
-            "bw_parent.hip", "bw_parent.h", "bw_parent_host.h")
+            "bw_parent.hip", "bw_parent.h", "bw_parent_host.h", "bw_walk.h", "bw_walk_host.h")
 
 
 def _code_only(text):

@@ -1,6 +1,6 @@
 // bw_restore.h -- private declarations of the restore session (bw_restore.hip): the locator's
-// tables, the tree parser's records and the gather's instance tables.  Off the chunk -> hash ->
-// dedup path (backuwup_amd/build.py OFF_PATH), like bw_unpack.h.
+// tables and the gather's instance tables (the tree parser's record, RsTreeHdr, is bw_store_layout.h's,
+// free of HIP).  Off the chunk -> hash -> dedup path (backuwup_amd/build.py OFF_PATH), like bw_unpack.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,16 +19,6 @@ constexpr uint32_t RS_EMPTY = 0xffffffffu;            // a free table slot (tabl
 constexpr uint64_t RS_SLOT_STRIDE = BW_BLOB_MAX_UNCOMPRESSED_SIZE + 32;  // a decode slot plus skew and load slack
 constexpr uint32_t RS_DEFAULT_SLOTS = 1024;           // 3 GiB of decode room
 constexpr uint64_t RS_MAX_INSTANCES = 1u << 20;       // instances of one sub-batch (bounds the tables)
-
-// What the tree parser reports for one blob (bincode::deserialize::<Tree>, trailing bytes allowed).
-struct RsTreeHdr {
-    uint32_t status;  // 0, or BW_RESTORE_EFORMAT
-    uint32_t kind, flags, has_next;
-    uint64_t size, mtime, ctime;
-    uint64_t name_pos, name_len;  // the name's bytes inside the blob
-    uint64_t ch_pos, n_children;  // the children's 32-byte rows inside the blob
-    uint8_t next[32];
-};
 
 // One instance of a sub-batch: the blob in decode slot `slot` is the next piece of the output
 // (valid = 0: the instance is dropped, its file failed earlier or the window is full).
@@ -256,8 +246,8 @@ struct bw_restore {
     DevBuf pr_bits, pr_front[2], pr_ctr, pr_err, pr_stat, pr_tab, pr_hdr;  // prune (bw_prune.hip)
     DevBuf ck_buf;  // check (bw_check.hip)
     DevBuf rk_buf;  // rekey (bw_rekey.hip)
-    // diff (bw_diff.hip): a level's nodes and references (this level, the next), chain rounds, tables and arenas
-    DevBuf df_nodes[2], df_refs[2], df_chain[2], df_out, df_take, df_stage, df_seghash, df_lvl, df_rows, df_rowseg;
-    DevBuf df_tab, df_rtab, df_rec, df_names, df_err, df_read, df_ctr;
-    DevBuf pm[24];  // parent match (bw_parent.hip): its buffers by PM_B_*
+    // the walks over the session; two calls never overlap (one stream, every entry point returns synchronised)
+    DevBuf wk[12];  // the tree-chain fetch they share (bw_walk.h): its buffers by WK_B_*
+    DevBuf df[12];  // diff (bw_diff.hip): its own buffers by DF_B_*
+    DevBuf pm[12];  // parent match (bw_parent.hip): its own buffers by PM_B_*
 };

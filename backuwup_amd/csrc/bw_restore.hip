@@ -335,12 +335,10 @@ extern "C" int bw_restore_close(bw_restore* s) {
     hipStreamSynchronize(s->c->stream);
     for (DevBuf* b : {&s->ids, &s->items, &s->d_entries, &s->id_tab, &s->item_tab, &s->item_pos, &s->entry_tab, &s->slot_buf,
                       &s->q, &s->tab, &s->run, &s->emit, &s->win, &s->pf_buf, &s->pr_bits, &s->pr_front[0],
-                      &s->pr_front[1], &s->pr_ctr, &s->pr_err, &s->pr_stat, &s->pr_tab, &s->pr_hdr, &s->ck_buf, &s->rk_buf, &s->df_nodes[0],
-                      &s->df_nodes[1], &s->df_refs[0], &s->df_refs[1], &s->df_chain[0], &s->df_chain[1], &s->df_out, &s->df_take,
-                      &s->df_stage, &s->df_seghash, &s->df_lvl, &s->df_rows, &s->df_rowseg, &s->df_tab, &s->df_rtab, &s->df_rec,
-                      &s->df_names, &s->df_err, &s->df_read, &s->df_ctr})
+                      &s->pr_front[1], &s->pr_ctr, &s->pr_err, &s->pr_stat, &s->pr_tab, &s->pr_hdr, &s->ck_buf, &s->rk_buf})
         free_dev(*b);
-    for (DevBuf& b : s->pm) free_dev(b);
+    for (auto* walk : {&s->wk, &s->df, &s->pm})
+        for (DevBuf& b : *walk) free_dev(b);
     delete s;
     return BW_OK;
 }

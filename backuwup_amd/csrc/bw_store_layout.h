@@ -23,6 +23,16 @@ namespace bw {
 
 constexpr uint32_t RS_PIECE = 32768;  // bytes of one instance (a blob, a gap) that a wave copies
 
+// What the tree parser reports for one blob (bincode::deserialize::<Tree>, trailing bytes allowed).
+struct RsTreeHdr {
+    uint32_t status;  // 0, or BW_RESTORE_EFORMAT
+    uint32_t kind, flags, has_next;
+    uint64_t size, mtime, ctime;
+    uint64_t name_pos, name_len;  // the name's bytes inside the blob
+    uint64_t ch_pos, n_children;  // the children's 32-byte rows inside the blob
+    uint8_t next[32];
+};
+
 // BW_UNPACK_ERANGE, the one statement of it (the unpack chain, prune's mark and plan, check, rekey):
 // the entry's nonce + sealed bytes lie inside the packfile's blob section, and the sealed bytes hold a tag
 BW_HOST_DEVICE static inline bool rs_range_ok(uint64_t size, uint64_t header_len, uint64_t offset, uint64_t length) {

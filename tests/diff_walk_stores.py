@@ -4,7 +4,28 @@ import numpy as np
 
 import diff_stores as ds
 
+import restore_store as rs
+
 WIDE = 300
+
+
+def chain_names_itself():
+    """On side B the Dir `loop` is one piece whose next_sibling is its own hash, between the sound siblings
+    `before` and `after` (their mtimes change, so both give records); side A holds a sound Dir of the
+    same name.  The walk follows the chain for as many pieces as the store has entries and refuses the
+    next round unread.  info: loop = the looping hash, n_entries = the store's entries."""
+    rng = np.random.default_rng(62)
+    b = rs.Builder(seed=62)
+    kid = b.add_file("in_loop", ds.blob(rng, 50))
+    data_before, data_after = ds.blob(rng, 60), ds.blob(rng, 70)
+    hl = b"\xab" * 32
+    ds.raw_tree(b, 1, "loop", [kid], sib=hl, blob_hash=hl)
+    sound = b.add_tree(1, "loop", None, None, None, [kid])
+    ra = b.add_tree(1, "", None, None, None, [b.add_file("before", data_before, 1000), sound, b.add_file("after", data_after, 1000)])
+    rb = b.add_tree(1, "", None, None, None, [b.add_file("before", data_before, 2000), hl, b.add_file("after", data_after, 2000)])
+    n_entries = len(b.blobs)
+    packs, index = b.finish(target=5)
+    return packs, index, ra, rb, dict(loop=hl, n_entries=n_entries)
 
 
 def wide_and_shared():

@@ -211,6 +211,31 @@ def test_damage_never_stops_the_walk(df):
     assert {r["b"][0] for r in records_v if r["flags"] & D.F_UNREADABLE} == unreadable | {info["cyc"]}
 
 
+def test_a_chain_that_names_itself_is_refused_after_as_many_pieces_as_the_store_has_entries(df):
+    import diff_walk_stores
+    case = diff_walk_stores.chain_names_itself()
+    hl, n_e = case[4]["loop"], case[4]["n_entries"]
+    R, D = df.ref, df.dref
+    store, hd, records, errors, read, levels = run(df, case)
+    assert n_e == 12 == len(df.pref.flat_entries(hd))
+    got = by_path(df, records)
+    assert sorted(got) == ["", "/after", "/before", "/loop"] and all(len(v) == 1 for v in got.values())
+    loop = got["/loop"][0]
+    assert loop["change"] == D.MODIFIED and loop["flags"] == D.F_TRUNCATED and loop["b"][0] == hl
+    assert loop["a"][6] == 1 and loop["b"][6] == n_e + 1            # pieces 0 .. n_e were read, one row each
+    assert (loop["common_prefix"], loop["n_new"]) == (1, 0)
+    assert dict(errors) == {(hl, hl, D.NONE, R.EFORMAT): 1}
+    for name in ("/before", "/after"):                              # the sound siblings are unaffected
+        r = got[name][0]
+        assert r["change"] == D.MODIFIED and r["flags"] == 0 and (r["a"][4], r["b"][4]) == (1000, 2000) and r["n_new"] == 0
+    assert got[""][0]["flags"] == 0 and levels == 2
+    # the other way round the looping side is A
+    _, _, back, errors_back, read_back, _ = run(df, case, swap=True)
+    loop = by_path(df, back)["/loop"][0]
+    assert loop["flags"] == D.F_TRUNCATED and loop["a"][6] == n_e + 1 and loop["b"][6] == 1
+    assert errors_back == errors and read_back == read
+
+
 @pytest.mark.parametrize("seed", range(20))
 def test_seeded_mutations_agree_with_two_listings(df, seed):
     case = df.stores.mutation(seed)

@@ -159,6 +159,18 @@ def test_damage_is_collected_and_the_walk_goes_on(ctx, df):
     assert counts["n_errors"] == len(errors) > 0
 
 
+def test_a_chain_that_names_itself_is_refused_unread(ctx, df):
+    # the fetch's bounded refusal (round > n_e) with the diff walk's hooks: one EFORMAT error, F_TRUNCATED
+    out = walk(ctx, df, "chain_names_itself", which=("ab", "ba"), slots=4)
+    hl = built("chain_names_itself")[0][4]["loop"]
+    L = sys.modules["backuwup_amd._lib"]
+    for w in ("ab", "ba"):
+        records, _, _, counts, errors = out[w]
+        assert [(bytes(e["hash"]), bytes(e["parent"]), int(e["child_pos"]), int(e["reason"])) for e in errors] == \
+            [(hl, hl, NONE, L.BW_RESTORE_EFORMAT)]
+        assert Counter(int(r["flags"]) for r in records) == {0: 3, df.diff.F_TRUNCATED: 1}
+
+
 @pytest.mark.parametrize("seed", [0, 4, 8, 12, 16])
 def test_seeded_mutations(ctx, df, seed):
     walk(ctx, df, "mutation", seed, slots=4 if seed % 8 else 16)
