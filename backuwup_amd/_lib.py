@@ -157,6 +157,34 @@ class BwParentCounts(ctypes.Structure):
                 ("n_unchanged", ctypes.c_uint64), ("unchanged_bytes", ctypes.c_uint64)]
 
 
+BW_IMPACT_SELF, BW_IMPACT_BELOW = 1, 2
+BW_IMPACT_UNREADABLE, BW_IMPACT_TRUNCATED, BW_IMPACT_CYCLIC = 1, 2, 4
+
+
+class BwImpactCounts(ctypes.Structure):
+    _fields_ = [("n_trees_expanded", ctypes.c_uint64), ("n_levels", ctypes.c_uint64), ("n_edges", ctypes.c_uint64),
+                ("n_sweeps", ctypes.c_uint64), ("n_tainted", ctypes.c_uint64), ("n_errors", ctypes.c_uint64),
+                ("n_roots_affected", ctypes.c_uint64)]
+
+
+class BwImpactRecord(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("root", ctypes.c_uint64), ("parent", ctypes.c_uint64),
+                ("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint64), ("kind", ctypes.c_uint32),
+                ("meta_flags", ctypes.c_uint32), ("size", ctypes.c_uint64), ("mtime", ctypes.c_uint64),
+                ("ctime", ctypes.c_uint64), ("n_children", ctypes.c_uint64), ("n_affected", ctypes.c_uint64),
+                ("first_affected", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class BwImpactRoot(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_uint64), ("n_files", ctypes.c_uint64), ("n_unreadable", ctypes.c_uint64),
+                ("lost_chunk_refs", ctypes.c_uint64)]
+
+
+class BwImpactPathsCounts(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_uint64), ("name_bytes", ctypes.c_uint64), ("n_levels", ctypes.c_uint64),
+                ("n_errors", ctypes.c_uint64)]
+
+
 BW_CHECK_E_RANGE, BW_CHECK_E_ORDER, BW_CHECK_E_UNINDEXED, BW_CHECK_E_SHADOWED = 1, 2, 4, 8
 BW_CHECK_SKIPPED, BW_CHECK_IDUPLICATE = 32, 33
 BW_CHECK_AUTH, BW_CHECK_FULL = 1, 2
@@ -324,6 +352,11 @@ SIGNATURES = [
     ("bw_parent_match", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(BwRestoreNode), ctypes.c_uint64,
                                        vp, ctypes.c_uint64, ctypes.POINTER(BwParentResult), u8p,
                                        ctypes.POINTER(BwParentCounts), ctypes.POINTER(BwPruneError), ctypes.c_uint64]),
+    ("bw_impact_mark", ctypes.c_int, [vp, vp, ctypes.c_uint64, u8p, ctypes.c_uint32, u8p, u8p, ctypes.POINTER(BwImpactCounts),
+                                      ctypes.POINTER(BwPruneError), ctypes.c_uint64]),
+    ("bw_impact_paths", ctypes.c_int, [vp, vp, ctypes.c_uint64, u8p, ctypes.c_uint32, ctypes.POINTER(BwImpactRecord),
+                                       ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(BwImpactRoot),
+                                       ctypes.POINTER(BwImpactPathsCounts), ctypes.POINTER(BwPruneError), ctypes.c_uint64]),
     ("bw_auth_device", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_auth", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_check_structure", ctypes.c_int, [vp, u8p, u8p, ctypes.POINTER(BwCheckPackfileStat),

@@ -50,6 +50,8 @@ struct DfFetch {
         return false;
     }
 
+    __device__ static bool refuse(const DfWalk&, uint64_t) { return false; }  // every located piece is opened
+
     __device__ static void lost(const DfWalk& w, uint32_t node) { atomicOr(&w.nodes[node].state, DF_TRUNC); }
 
     __device__ static void header(const DfWalk& w, uint32_t node, const RsTreeHdr& h, uint64_t name_off) {

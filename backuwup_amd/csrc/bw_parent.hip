@@ -40,6 +40,8 @@ struct PmFetch {
     static constexpr uint64_t ERRS_PER_REF = 1;
 
     __device__ static bool first(const PmWalk&, const WkRef&) { return false; }
+    __device__ static bool refuse(const PmWalk&, uint64_t) { return false; }  // every located piece is opened
+
     __device__ static void lost(const PmWalk&, uint32_t) {}
 
     __device__ static void header(const PmWalk& w, uint32_t child, const RsTreeHdr& h, uint64_t name_off) {

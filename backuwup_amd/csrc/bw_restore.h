@@ -250,4 +250,5 @@ struct bw_restore {
     DevBuf wk[12];  // the tree-chain fetch they share (bw_walk.h): its buffers by WK_B_*
     DevBuf df[12];  // diff (bw_diff.hip): its own buffers by DF_B_*
     DevBuf pm[12];  // parent match (bw_parent.hip): its own buffers by PM_B_*
+    DevBuf im[16];  // impact (bw_impact.hip): the mark's and the report walk's buffers by IM_B_*
 };

@@ -339,6 +339,7 @@ extern "C" int bw_restore_close(bw_restore* s) {
         free_dev(*b);
     for (auto* walk : {&s->wk, &s->df, &s->pm})
         for (DevBuf& b : *walk) free_dev(b);
+    for (DevBuf& b : s->im) free_dev(b);
     delete s;
     return BW_OK;
 }

@@ -1,5 +1,5 @@
 // bw_walk.h -- the tree-chain fetch that the walks over a restore session share (the diff walk,
-// bw_diff.hip, and the parent match, bw_parent.hip): n references through the unpack chain `slots` blobs
+// bw_diff.hip, the parent match, bw_parent.hip, and impact's report walk, bw_impact.hip): n references through the unpack chain `slots` blobs
 // at a time, round r fetching piece r of every next_sibling chain that has one.  Two kernels, written
 // once over a walk's policy type and instantiated by each walk:
 //   k_wk_resolve  one lane per reference: locate, kind, read[], and the walk's check of a first piece
@@ -11,6 +11,7 @@
 //   P::ROWS_TOO_MANY  the text for a level of more than P::MAX_ROWS children rows
 //   P::ERRS_PER_REF   the errors k_wk_resolve can write for one reference
 //   P::first(w, r)    resolve, a first piece: true when the owner is to be read for its header only
+//   P::refuse(w, e)   resolve: true when the located Tree entry e is not to be opened (it counts as unread)
 //   P::lost(w, owner) a later piece of the owner's chain could not be read
 //   P::header(w, owner, h, name_off)  take: where a first piece's header lands
 // Private; off the chunk -> hash -> dedup path (backuwup_amd/build.py OFF_PATH), like bw_restore.h.
@@ -146,6 +147,8 @@ __global__ void __launch_bounds__(256) k_wk_resolve(typename Pol::Walk w, const 
         wk_error(w.f, r.hash, r.by, r.by_pos, st);
     } else if (w.f.loc.entries[e].kind != BW_BLOB_TREE) {
         wk_error(w.f, r.hash, r.by, r.by_pos, BW_RESTORE_ENOTTREE);
+    } else if (Pol::refuse(w, e)) {
+        // the walk does not open it, and that is no error of the fetch's
     } else {
         w.f.read[e] = 1;
         res = e;

@@ -758,6 +758,118 @@ private:
     const std::vector<bw_unpack_entry>& entries_;
 };
 
+// ------------------------------------------------------------------ impact (no counterpart in the reference)
+// Over an open Restore: mark() = the taint of every entry the roots reach when the entries of `bad` are
+// lost (a lost tree blob is never opened), paths() = the affected paths under each root, opening nothing
+// else.  Errors are collected and never end a call.
+class Impact {
+public:
+    struct Mark {
+        std::vector<uint8_t> taint;          // one byte per header entry: BW_IMPACT_SELF | BW_IMPACT_BELOW
+        std::vector<uint8_t> root_affected;  // one byte per root
+        bw_impact_counts counts{};
+        std::vector<bw_prune_error> errors;  // in no particular order
+    };
+    struct Paths {
+        std::vector<bw_impact_record> records;  // a parent before its children
+        std::vector<uint8_t> names;
+        std::vector<bw_impact_root> per_root;
+        bw_impact_paths_counts counts{};
+        std::vector<bw_prune_error> errors;
+
+        std::string name(size_t i) const {
+            const bw_impact_record& r = records[i];
+            return std::string(names.begin() + r.name_off, names.begin() + r.name_off + r.name_len);
+        }
+        // the names joined through parent; a root's path is empty, an unreadable item's name is "?"
+        std::string path(size_t i) const {
+            const bw_impact_record& r = records[i];
+            const std::string own = (r.flags & BW_IMPACT_UNREADABLE) ? "?" : name(i);
+            if (r.parent == ~0ull) return (r.flags & BW_IMPACT_UNREADABLE) ? own : "";
+            const std::string up = path(r.parent);
+            return up.empty() ? own : up + "/" + own;
+        }
+    };
+
+    Impact(Context& ctx, Restore& session, const std::vector<bw_unpack_entry>& entries)
+        : ctx_(ctx), s_(session), entries_(entries) {}
+
+    // the what-if vector: every entry of the packfiles at these positions
+    std::vector<uint8_t> lost_packfiles(const std::vector<uint32_t>& positions) const {
+        std::vector<uint8_t> bad(entries_.size(), 0);
+        for (size_t e = 0; e < entries_.size(); e++)
+            for (uint32_t p : positions)
+                if (entries_[e].packfile == p) bad[e] = 1;
+        return bad;
+    }
+
+    // bad: one byte per header entry, or empty: nothing is lost
+    Mark mark(const std::vector<BlobHash>& roots, const std::vector<uint8_t>& bad, bool verify = false) {
+        if (!bad.empty() && bad.size() != entries_.size()) throw Error(BW_EINVAL, "impact: bad holds another number of entries");
+        Mark m;
+        m.taint.resize(entries_.size() + 1);
+        m.root_affected.resize(roots.size() + 1);
+        const std::vector<uint8_t> flat = flat_roots(roots);
+        uint64_t ecap = 64;
+        for (;;) {
+            m.errors.resize(ecap + 1);
+            const int rc = bw_impact_mark(s_.get(), flat.data(), roots.size(), bad.empty() ? nullptr : bad.data(),
+                                          verify ? BW_UNPACK_VERIFY : 0, m.taint.data(), m.root_affected.data(), &m.counts,
+                                          m.errors.data(), ecap);
+            if (rc != BW_ENOSPC) {
+                check(rc, ctx_.get());
+                break;
+            }
+            ecap = m.counts.n_errors;
+        }
+        m.taint.resize(entries_.size());
+        m.root_affected.resize(roots.size());
+        m.errors.resize(m.counts.n_errors);
+        return m;
+    }
+
+    // taint as mark() returned it; the buffers grow until the walk fits them
+    Paths paths(const std::vector<BlobHash>& roots, const std::vector<uint8_t>& taint, bool verify = false) {
+        if (taint.size() != entries_.size()) throw Error(BW_EINVAL, "impact: taint holds another number of entries");
+        Paths d;
+        const std::vector<uint8_t> flat = flat_roots(roots);
+        uint64_t rcap = 1024, ncap = 1 << 16, ecap = 64;
+        for (;;) {
+            d.records.resize(rcap + 1);
+            d.names.resize(ncap + 1);
+            d.errors.resize(ecap + 1);
+            d.per_root.assign(roots.size() + 1, bw_impact_root{});
+            const int rc = bw_impact_paths(s_.get(), flat.data(), roots.size(), taint.data(), verify ? BW_UNPACK_VERIFY : 0,
+                                           d.records.data(), rcap, d.names.data(), ncap, d.per_root.data(), &d.counts,
+                                           d.errors.data(), ecap);
+            if (rc != BW_ENOSPC) {
+                check(rc, ctx_.get());
+                break;
+            }
+            // the counts are the totals up to the level that did not fit
+            if (d.counts.n_records > rcap) rcap = std::max<uint64_t>(2 * rcap, d.counts.n_records);
+            if (d.counts.name_bytes > ncap) ncap = std::max<uint64_t>(2 * ncap, d.counts.name_bytes);
+            if (d.counts.n_errors > ecap) ecap = d.counts.n_errors;
+        }
+        d.records.resize(d.counts.n_records);
+        d.names.resize(d.counts.name_bytes);
+        d.errors.resize(d.counts.n_errors);
+        d.per_root.resize(roots.size());
+        return d;
+    }
+
+private:
+    static std::vector<uint8_t> flat_roots(const std::vector<BlobHash>& roots) {
+        std::vector<uint8_t> flat(32 * roots.size() + 1);
+        for (size_t i = 0; i < roots.size(); i++) std::copy(roots[i].begin(), roots[i].end(), flat.begin() + 32 * i);
+        return flat;
+    }
+
+    Context& ctx_;
+    Restore& s_;
+    const std::vector<bw_unpack_entry>& entries_;
+};
+
 // ------------------------------------------------------------------ check (no counterpart in the reference)
 // Over an open Restore: structure() = headers against index items and the layout of every blob
 // section, data() = every selected entry's bytes (BW_CHECK_AUTH: tags only, BW_CHECK_FULL: the unpack

@@ -590,6 +590,107 @@ int bw_parent_match(bw_restore* session, const uint8_t* parent_root, uint64_t tr
                     bw_parent_result* results, uint8_t* read, bw_parent_counts* counts, bw_prune_error* errs,
                     uint64_t err_cap);
 
+/* ---- impact: which files of which snapshots a set of lost blobs takes down ----
+ * The reference cannot ask this; restic answers it with find --blob / --pack.  Two steps over an open
+ * restore session, both synchronous: bw_impact_mark gives every reached entry its taint (each distinct
+ * tree blob is opened once, as in bw_prune_mark), bw_impact_paths goes down from the roots and opens
+ * only affected paths (as bw_diff_trees opens only changed ones). */
+#define BW_IMPACT_SELF 1u  /* the entry's own bytes are lost or refused               */
+#define BW_IMPACT_BELOW 2u /* an expanded Tree entry with an affected reference       */
+typedef struct bw_impact_counts {
+    uint64_t n_trees_expanded; /* tree blobs opened, parsed and expanded (bw_prune_mark's figure without bad[]) */
+    uint64_t n_levels;         /* rounds of the walk                                                            */
+    uint64_t n_edges;          /* references of expanded pieces that resolve to a Tree entry                    */
+    uint64_t n_sweeps;         /* sweeps over the edge list, the one that changed nothing included (>= 1)       */
+    uint64_t n_tainted;        /* entries with any taint bit                                                    */
+    uint64_t n_errors;         /* always the full number                                                        */
+    uint64_t n_roots_affected;
+} bw_impact_counts;
+
+/* bad (host, one byte per session entry, or NULL: none): nonzero = treat this entry's bytes as lost.
+ * A Tree entry with bad[e] set is never opened, so a what-if question corrupts and reads nothing.
+ * flags: BW_UNPACK_VERIFY or 0; chunk payloads are never read, so a damaged chunk that bad[] does not
+ * name is not found here (bw_check_data finds it, and its status feeds bad[]).
+ *   The walk is bw_prune_mark's, with its rules: level-synchronous from the roots; a frontier of Tree
+ * entries not yet expanded goes through the unpack chain `slots` at a time; each distinct Tree entry
+ * is expanded once; a hash held by several entries means the entry bw_restore_locate resolves it to;
+ * cycles end by themselves.
+ *   taint[e] (host, one byte per session entry) is 0 for an entry no root reaches, else the OR of:
+ * BW_IMPACT_SELF, set when the entry is reached and bad[e] is nonzero, or it is a Tree entry reached
+ * by a tree reference that the unpack chain or the parser refuses (BW_UNPACK_ERANGE / _ETAG / _EZSTD /
+ * _EDIGEST, BW_RESTORE_EFORMAT), or it is a FileChunk entry whose range fails prune's range rule;
+ * BW_IMPACT_BELOW, set on an expanded Tree entry that has an affected reference among its children
+ * rows and its next_sibling.  A reference is affected when locate fails; or it is a tree reference (a
+ * Dir row, a next_sibling, a root) that resolves to a FileChunk entry; or it is a tree reference and
+ * the entry it resolves to has any taint bit; or it is a row of a File piece and the entry it resolves
+ * to has SELF.  File rows look only at SELF because they are never opened; this is conservative in
+ * one case: a tree-kind blob that the parser refuses (SELF) but that a File also names as a chunk,
+ * which a restore would still read.  BELOW is the least fixed point of that rule over the graph of
+ * expanded blobs: the expand kernel settles rows that resolve to FileChunk entries at once and appends
+ * an 8-byte (parent entry, child entry) edge for every reference that resolves to a Tree entry; a
+ * propagate kernel sweeps the edge list, latest level first, and the sweep is repeated until one
+ * changes nothing.
+ *   root_affected[r] (host, one byte per root) = 1 when root r's reference is affected.  Errors are
+ * bw_prune_mark's records with its meaning and never stop the walk; bad[] itself produces no error
+ * record.  counts->n_errors > err_cap -> BW_ENOSPC with everything else filled.  An edge names an
+ * entry in 31 bits: a session of 2^31 entries or more -> BW_ENOMEM. */
+int bw_impact_mark(bw_restore* session, const uint8_t* roots, uint64_t n_roots, const uint8_t* bad, uint32_t flags,
+                   uint8_t* taint, uint8_t* root_affected, bw_impact_counts* counts, bw_prune_error* errs,
+                   uint64_t err_cap);
+
+#define BW_IMPACT_UNREADABLE 1u /* the first piece is SELF, unlocatable or not a tree: hash only, empty name, not descended */
+#define BW_IMPACT_TRUNCATED 2u  /* a later piece of the chain is lost: the list ends there                                  */
+#define BW_IMPACT_CYCLIC 4u     /* the hash is one of its own ancestors' on this path: its list counts as empty             */
+typedef struct bw_impact_record {
+    uint8_t hash[32];
+    uint64_t root;   /* the index of the root it lies under                                              */
+    uint64_t parent; /* the record of the item above, ~0 for a root; always lower than the record's own */
+    uint64_t name_off, name_len; /* into `names`; empty for an unreadable item                          */
+    uint32_t kind;       /* BW_TREE_FILE or BW_TREE_DIR */
+    uint32_t meta_flags; /* BW_TREE_HAS_*               */
+    uint64_t size, mtime, ctime;
+    uint64_t n_children;     /* the rows read: its whole next_sibling chain, as far as it could be read */
+    uint64_t n_affected;     /* the affected ones among them                                            */
+    uint64_t first_affected; /* the position of the first in the list, ~0 when none                     */
+    uint32_t flags;          /* BW_IMPACT_UNREADABLE / _TRUNCATED / _CYCLIC                             */
+    uint32_t pad;
+} bw_impact_record;
+typedef struct bw_impact_root {
+    uint64_t n_records, n_files, n_unreadable; /* records under the root; the File ones; the UNREADABLE ones */
+    uint64_t lost_chunk_refs;                  /* the sum of the File records' n_affected                     */
+} bw_impact_root;
+typedef struct bw_impact_paths_counts {
+    uint64_t n_records, name_bytes;
+    uint64_t n_levels; /* levels of the walk that hold a record */
+    uint64_t n_errors; /* always the full number                */
+} bw_impact_paths_counts;
+
+/* taint: host, one byte per session entry, as bw_impact_mark returned it (any other bit -> BW_EINVAL);
+ * it is uploaded once.  flags: BW_UNPACK_VERIFY or 0.  The walk is a third policy over the tree-chain
+ * fetch that the diff walk and the parent match share.
+ *   An item is (root index, parent record, tree reference); level 0 holds the affected roots in root
+ * order (a root is affected by the rule above).  Per item the first piece is read for its header and
+ * name, the whole next_sibling chain is fetched and the rows are concatenated in chain order.  An
+ * entry with SELF is never opened.  For a Dir the affected rows become the next level's items;
+ * unaffected rows are not opened, so an intact subtree costs nothing.  For a File the affected rows
+ * are counted.  Each item gives one record; a level's records follow its items' order.
+ *   The same subtree under two roots, or twice under one root, gives records under each: paths belong
+ * to snapshots.  per_root[r] (host, one per root) sums the records returned.
+ *   Errors never stop the walk and use prune's record with the diff walk's meaning; they are what
+ * opening the items meets: a locate status or BW_RESTORE_ENOTTREE for an item's reference, a chain or
+ * parser refusal of a piece that taint does not name, and BW_RESTORE_EFORMAT for a CYCLIC item or a
+ * chain of more pieces than the store has entries.  A piece that is not opened because of SELF gives
+ * no error here: bw_impact_mark reported it, or bad[] named it.
+ *   Capacity and hard limit are bw_diff_trees' word for word: the walk stops at the first level whose
+ * records or names do not fit and returns BW_ENOSPC with counts holding the totals up to and including
+ * that level; the levels before it are filled in, and nothing is written past a cap; per_root is
+ * partial then: it sums the levels that were filled in, not the level counts stops at.  counts->n_errors
+ * > err_cap -> BW_ENOSPC with everything else filled.  A level is indexed in 32 bits: more than 2^30
+ * items or rows in a level ends the call with BW_ENOMEM. */
+int bw_impact_paths(bw_restore* session, const uint8_t* roots, uint64_t n_roots, const uint8_t* taint, uint32_t flags,
+                    bw_impact_record* records, uint64_t record_cap, uint8_t* names, uint64_t names_cap,
+                    bw_impact_root* per_root, bw_impact_paths_counts* counts, bw_prune_error* errs, uint64_t err_cap);
+
 /* ---- check: is this store sound, are these bytes still the bytes that were sealed ----
  * The reference never verifies what it has written; this goes past it as prune does.  Three layers,
  * all synchronous: bw_auth(_device) recomputes AES-GCM tags without decrypting, bw_check_structure

@@ -298,6 +298,57 @@ pub mod ffi {
 
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_impact_counts {
+        pub n_trees_expanded: u64,
+        pub n_levels: u64,
+        pub n_edges: u64,
+        pub n_sweeps: u64,
+        pub n_tainted: u64,
+        pub n_errors: u64,
+        pub n_roots_affected: u64,
+    }
+
+    /// One item of `bw_impact_paths`: an affected path under one root (flags: BW_IMPACT_UNREADABLE 1, _TRUNCATED 2, _CYCLIC 4).
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_impact_record {
+        pub hash: [u8; 32],
+        pub root: u64,
+        pub parent: u64,
+        pub name_off: u64,
+        pub name_len: u64,
+        pub kind: u32,
+        pub meta_flags: u32,
+        pub size: u64,
+        pub mtime: u64,
+        pub ctime: u64,
+        pub n_children: u64,
+        pub n_affected: u64,
+        pub first_affected: u64,
+        pub flags: u32,
+        pub pad: u32,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_impact_root {
+        pub n_records: u64,
+        pub n_files: u64,
+        pub n_unreadable: u64,
+        pub lost_chunk_refs: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_impact_paths_counts {
+        pub n_records: u64,
+        pub name_bytes: u64,
+        pub n_levels: u64,
+        pub n_errors: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
     pub struct bw_check_packfile_stat {
         pub n_entries: u64,
         pub n_range: u64,
@@ -579,6 +630,14 @@ pub mod ffi {
         pub fn bw_parent_match(session: *mut bw_restore, parent_root: *const u8, trust_before: u64, flags: u32,
                                nodes: *const bw_restore_node, n_nodes: u64, names: *const u8, names_len: u64,
                                results: *mut bw_parent_result, read: *mut u8, counts: *mut bw_parent_counts,
+                               errs: *mut bw_prune_error, err_cap: u64) -> c_int;
+
+        pub fn bw_impact_mark(session: *mut bw_restore, roots: *const u8, n_roots: u64, bad: *const u8, flags: u32,
+                              taint: *mut u8, root_affected: *mut u8, counts: *mut bw_impact_counts,
+                              errs: *mut bw_prune_error, err_cap: u64) -> c_int;
+        pub fn bw_impact_paths(session: *mut bw_restore, roots: *const u8, n_roots: u64, taint: *const u8, flags: u32,
+                               records: *mut bw_impact_record, record_cap: u64, names: *mut u8, names_cap: u64,
+                               per_root: *mut bw_impact_root, counts: *mut bw_impact_paths_counts,
                                errs: *mut bw_prune_error, err_cap: u64) -> c_int;
 
         pub fn bw_auth_device(ctx: *mut bw_ctx, prk: *const u8, d_src: *const u8, src_off: *const u64,
