@@ -185,6 +185,26 @@ class BwImpactPathsCounts(ctypes.Structure):
                 ("n_errors", ctypes.c_uint64)]
 
 
+BW_RETAIN_MAX_ROOTS = 4096
+
+
+class BwRetainRoot(ctypes.Structure):
+    _fields_ = [("reached_blobs", ctypes.c_uint64), ("reached_bytes", ctypes.c_uint64), ("unique_blobs", ctypes.c_uint64),
+                ("unique_bytes", ctypes.c_uint64), ("n_damaged", ctypes.c_uint64), ("status", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
+class BwRetainCounts(ctypes.Structure):
+    _fields_ = [("n_trees_expanded", ctypes.c_uint64), ("n_levels", ctypes.c_uint64), ("n_edges", ctypes.c_uint64),
+                ("n_sweeps", ctypes.c_uint64), ("n_errors", ctypes.c_uint64), ("reached_blobs", ctypes.c_uint64),
+                ("reached_bytes", ctypes.c_uint64), ("orphan_blobs", ctypes.c_uint64), ("orphan_bytes", ctypes.c_uint64)]
+
+
+class BwRetainFreed(ctypes.Structure):
+    _fields_ = [("freed_blobs", ctypes.c_uint64), ("freed_bytes", ctypes.c_uint64), ("live_blobs", ctypes.c_uint64),
+                ("live_bytes", ctypes.c_uint64)]
+
+
 BW_CHECK_E_RANGE, BW_CHECK_E_ORDER, BW_CHECK_E_UNINDEXED, BW_CHECK_E_SHADOWED = 1, 2, 4, 8
 BW_CHECK_SKIPPED, BW_CHECK_IDUPLICATE = 32, 33
 BW_CHECK_AUTH, BW_CHECK_FULL = 1, 2
@@ -357,6 +377,10 @@ SIGNATURES = [
     ("bw_impact_paths", ctypes.c_int, [vp, vp, ctypes.c_uint64, u8p, ctypes.c_uint32, ctypes.POINTER(BwImpactRecord),
                                        ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(BwImpactRoot),
                                        ctypes.POINTER(BwImpactPathsCounts), ctypes.POINTER(BwPruneError), ctypes.c_uint64]),
+    ("bw_retain_mark", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint32, u64p, u8p, ctypes.POINTER(BwRetainRoot),
+                                      ctypes.POINTER(BwRetainCounts), ctypes.POINTER(BwPruneError), ctypes.c_uint64]),
+    ("bw_retain_drop", ctypes.c_int, [vp, u64p, ctypes.c_uint64, u64p, ctypes.c_uint64, u8p,
+                                      ctypes.POINTER(BwPrunePackfileStat), ctypes.POINTER(BwRetainFreed)]),
     ("bw_auth_device", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_auth", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_check_structure", ctypes.c_int, [vp, u8p, u8p, ctypes.POINTER(BwCheckPackfileStat),

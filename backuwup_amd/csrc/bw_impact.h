@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/backuwup_gpu.h"
 #include "bw_walk.h"
 #include "bw_impact_host.h"
@@ -21,7 +23,7 @@ constexpr uint64_t IM_ERR_DEVICE = 65536;  // records of the device error list o
 constexpr uint64_t IM_MAX_ROWS = 1ull << 30;  // the report walk indexes a level in 32 bits
 
 // counters of the mark
-enum { IM_C_NEXT = 0, IM_C_ERRORS = 1, IM_C_EXPANDED = 2, IM_C_EDGES = 3, IM_C_CHANGED = 4, IM_C_DROPPED = 5, IM_C_COUNT = 8 };
+enum { IM_C_NEXT = 0, IM_C_ERRORS = 1, IM_C_EXPANDED = 2, IM_C_EDGES = 3, IM_C_CHANGED = 4, IM_C_DROPPED = 5, IM_C_LEAF = 6, IM_C_COUNT = 8 };
 // the report walk's counter behind WK_C_ERRORS
 enum { IM_C_ITEMS = 1 };
 static_assert(IM_C_ITEMS < WK_C_COUNT, "the counters fit the fetch's buffer");
@@ -50,7 +52,40 @@ struct ImMark {
     uint64_t err_cap;
     ImEdge* edges;
     uint64_t edge_cap;
+    ImEdge* leaf;  // RtReach: the edges that pass nothing on (IM_C_LEAF of them, edge_cap places too); else null
 };
+
+// What the mark's walk leaves to the walk that uses it, as the tree-chain fetch has ImFetch, DfFetch and
+// PmFetch.  ALL_EDGES false: an edge per reference that resolves to a Tree entry, a chunk's taint settles
+// into its parent's BELOW at once (impact).  ALL_EDGES true: an edge per reference that locates; those that
+// can pass something on (a tree reference to a Tree entry) go to `edges` by level, the rest to `leaf`, and
+// BELOW is set only for a reference that fails to locate or is a tree reference to a chunk (retain,
+// bw_retain.hip: SELF | BELOW is then the entry's own damage, and nothing is propagated over them).
+struct ImTaint {
+    static constexpr bool ALL_EDGES = false;
+};
+struct RtReach {
+    static constexpr bool ALL_EDGES = true;
+};
+
+// What im_walk leaves: on the device the bits, the edge lists and the counters (w), here the rest.
+struct ImWalked {
+    ImMark w;
+    ImLevels levels;  // `edges` by the level that appended them
+    uint64_t ctr[IM_C_COUNT];
+    std::vector<bw_prune_error> herr;  // what the chain refused: the host knows it first
+    uint8_t* d_out;    // out_bytes of IM_B_OUT for the caller's results
+    uint8_t* d_roots;  // behind them, the roots
+};
+
+// The walk both marks share (bw_impact.hip): roots, frontier loop, expansion.  dev_cap: the records of
+// the device error list.  leaf: the buffer of the leaf edges (RtReach), or null.
+template <class Pol>
+int im_walk(bw_restore* s, const uint8_t* roots, uint64_t n_roots, const uint8_t* bad, uint32_t flags, uint64_t dev_cap,
+            uint64_t out_bytes, DevBuf* leaf, ImWalked& wd);
+// The walk's errors to the caller's list, bw_prune_mark's way: *n_dev = what the kernels met, *n_errors = all.
+int im_errors_out(bw_restore* s, const ImWalked& wd, const char* walk, bw_prune_error* errs, uint64_t err_cap, uint64_t dev_cap,
+                  uint64_t* n_dev, uint64_t* n_errors);
 
 constexpr uint32_t IM_OK = 1;      // the item's first piece was read and parsed
 constexpr uint32_t IM_CYCLIC = 2;  // its hash is one of its ancestors': its list counts as empty

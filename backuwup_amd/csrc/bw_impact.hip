@@ -1,8 +1,9 @@
 // bw_impact.hip -- impact (include/backuwup_gpu_pack.h, "impact"): which files of which snapshots a set
 // of lost blobs takes down.  The reference cannot ask it.  Two walks over a restore session:
 //   the mark    prune's level-synchronous walk (each distinct tree blob through the unpack chain once)
-//               with a taint beside the reached bit: k_im_roots, k_im_expand (locate, SELF, the rows that
-//               settle at once, the edge list), k_im_propagate (BELOW to its least fixed point, one sweep
+//               with a taint beside the reached bit: im_walk<Pol> (k_im_roots, k_im_expand: locate, SELF, the
+//               rows that settle at once, the edge list; shared with retain, bw_retain.hip, which runs it under
+//               the RtReach policy), then impact's own half: k_im_propagate (BELOW to its least fixed point, one sweep
 //               per launch series, repeated by the host until a sweep changes nothing), k_im_taint,
 //               k_im_root_affected
 //   the report  a third policy over the tree-chain fetch (bw_walk.h) beside the diff walk's and the
@@ -44,11 +45,12 @@ __device__ static inline uint32_t im_shift(uint64_t e) { return 8 * (uint32_t)(e
 
 // One reference per lane; every lane of the wave calls this (active = the lane has a reference).  self
 // = the expanded entry that holds the references, RS_EMPTY for the roots (which append no edge and have
-// nobody to give BELOW to).  The places in the next frontier and in the edge list come per wave from one
-// atomic each (wk_wave_place).
+// nobody to give BELOW to).  The places in the next frontier and in the edge lists come per wave from one
+// atomic each (wk_wave_place).  Pol: which references become edges and what settles at once (bw_impact.h).
+template <class Pol>
 __device__ static void im_visit(const ImMark& w, bool active, const uint8_t* key, bool tree_ref, const uint8_t* parent,
                                 uint64_t child_pos, uint32_t self) {
-    bool push = false, edge = false, affected = false;
+    bool push = false, edge = false, leaf = false, affected = false;
     uint64_t e = ~0ull;
     if (active) {
         const uint8_t st = rs_locate_one(w.loc, key, e);
@@ -70,8 +72,13 @@ __device__ static void im_visit(const ImMark& w, bool active, const uint8_t* key
                 affected = true;
             }
             if (range_bad && !(old & (IM_REACHED << sh))) im_error(w, en.hash, nullptr, ~0ull, BW_UNPACK_ERANGE);
-            if (!tree) affected = affected || lost || range_bad;  // settled at once: a chunk's SELF never changes
-            edge = tree;
+            if (Pol::ALL_EDGES) {
+                edge = tree_ref && tree;  // only these pass something on
+                leaf = !edge;
+            } else {
+                if (!tree) affected = affected || lost || range_bad;  // settled at once: a chunk's SELF never changes
+                edge = tree;
+            }
             push = queue && !(old & (IM_QUEUED << sh));
         }
     }
@@ -83,18 +90,27 @@ __device__ static void im_visit(const ImMark& w, bool active, const uint8_t* key
         if (eat < w.edge_cap) w.edges[eat] = ImEdge{self, (uint32_t)e | (tree_ref ? 0u : IM_EDGE_SELF_ONLY)};
         else atomicAdd((unsigned long long*)&w.ctr[IM_C_DROPPED], 1ull);  // the host sized the list: it refuses the walk
     }
+    if (Pol::ALL_EDGES) {
+        const uint64_t lat = wk_wave_place(leaf, &w.ctr[IM_C_LEAF]);
+        if (leaf) {
+            if (lat < w.edge_cap) w.leaf[lat] = ImEdge{self, (uint32_t)e | (tree_ref ? 0u : IM_EDGE_SELF_ONLY)};
+            else atomicAdd((unsigned long long*)&w.ctr[IM_C_DROPPED], 1ull);
+        }
+    }
     const uint64_t bal = __ballot(affected);
     if (bal && (threadIdx.x & 63) == (uint32_t)__ffsll((unsigned long long)bal) - 1)
         atomicOr(&w.bits[self >> 2], IM_BELOW << im_shift(self));
 }
 
+template <class Pol>
 __global__ void __launch_bounds__(256) k_im_roots(ImMark w, const uint8_t* roots, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    im_visit(w, i < n, roots + 32 * (i < n ? i : 0), true, nullptr, i, RS_EMPTY);
+    im_visit<Pol>(w, i < n, roots + 32 * (i < n ? i : 0), true, nullptr, i, RS_EMPTY);
 }
 
 // Workgroup (b, y): tree blob b of the sub-batch, its references y * 256 + t, stepping by IM_EXPAND_Y *
 // 256 (k_prune_expand's shape).  The rows are read where the parser found them in the decode slot.
+template <class Pol>
 __global__ void __launch_bounds__(256) k_im_expand(ImMark w, const uint64_t* front, const uint8_t* slots,
                                                    const uint64_t* off, const RsTreeHdr* hdr, const uint32_t* cst, uint64_t m) {
     const uint64_t b = blockIdx.x;
@@ -117,7 +133,7 @@ __global__ void __launch_bounds__(256) k_im_expand(ImMark w, const uint64_t* fro
     for (uint64_t r0 = (uint64_t)blockIdx.y * 256; r0 < nrefs; r0 += (uint64_t)IM_EXPAND_Y * 256) {
         const uint64_t r = r0 + threadIdx.x;
         const bool child = r < nch;
-        im_visit(w, r < nrefs, child ? rows + 32 * r : h.next, dir || !child, self, child ? r : ~0ull, (uint32_t)se);
+        im_visit<Pol>(w, r < nrefs, child ? rows + 32 * r : h.next, dir || !child, self, child ? r : ~0ull, (uint32_t)se);
     }
 }
 
@@ -168,15 +184,16 @@ static void im_host_error(std::vector<bw_prune_error>& v, const uint8_t* hash, u
 
 static int im_refuse(bw_ctx* c, const char* why) { return wk_refuse(c, "impact", why); }
 
-// One walk with a device error list of dev_cap <= err_cap records; *n_dev_out = the errors the kernels met.
-// The frontier loop and the second-walk rule are pr_mark_once's and bw_prune_mark's (bw_prune.hip), written
-// beside them so that prune returns what it returned: a fix to either loop belongs in both.
-static int im_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, const uint8_t* bad, uint32_t flags,
-                        uint8_t* taint, uint8_t* root_affected, bw_impact_counts* counts, bw_prune_error* errs,
-                        uint64_t err_cap, uint64_t dev_cap, uint64_t* n_dev_out) {
+// The walk the two marks share (impact's below, retain's in bw_retain.hip): the roots, the frontier loop
+// and the expansions, with a device error list of dev_cap records.  It leaves the bits, the edge lists by
+// level and the counters on the device and synchronises.  The frontier loop and the second-walk rule are
+// pr_mark_once's and bw_prune_mark's (bw_prune.hip), written beside them so that prune returns what it
+// returned: a fix to either loop belongs in both.
+template <class Pol>
+int bw::im_walk(bw_restore* s, const uint8_t* roots, uint64_t n_roots, const uint8_t* bad, uint32_t flags, uint64_t dev_cap,
+                uint64_t out_bytes, DevBuf* leaf, ImWalked& wd) {
     const uint64_t n_e = s->entries.size(), n_pf = s->pf.size();
     bw_ctx* c = s->c;
-    memset(counts, 0, sizeof(*counts));
 
     const uint64_t words = (n_e + 3) / 4;
     if (int rc = ensure(c, s->im[IM_B_BITS], 4 * words + 16)) return rc;
@@ -186,12 +203,12 @@ static int im_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, c
     if (int rc = ensure(c, s->im[IM_B_ERR], dev_cap * sizeof(bw_prune_error) + 16)) return rc;
     if (int rc = ensure(c, s->im[IM_B_PF], n_pf * sizeof(PrPackfile) + 16)) return rc;
     if (int rc = ensure(c, s->im[IM_B_BAD], n_e + 16)) return rc;
-    // the results and, behind them, the roots (s->q is the parser's): [taint | root_affected | roots]
-    const uint64_t ra_at = (n_e + 15) & ~15ull, roots_at = ra_at + ((n_roots + 15) & ~15ull);
-    if (int rc = ensure(c, s->im[IM_B_OUT], roots_at + 32 * n_roots + 16)) return rc;
+    // the caller's results and, behind them, the roots (s->q is the parser's)
+    if (int rc = ensure(c, s->im[IM_B_OUT], out_bytes + 32 * n_roots + 16)) return rc;
     if (int rc = ensure(c, s->q, sizeof(RsTreeHdr) * (uint64_t)s->slots + 16)) return rc;
-    uint8_t* d_taint = P<uint8_t>(s->im[IM_B_OUT]);
-    uint8_t *d_ra = d_taint + ra_at, *d_roots = d_taint + roots_at;
+    wd.d_out = P<uint8_t>(s->im[IM_B_OUT]);
+    wd.d_roots = wd.d_out + out_bytes;
+    uint8_t* d_roots = wd.d_roots;
     const std::vector<PrPackfile> hpf = rs_packfile_table(s);
     HIPCHK(c, hipMemsetAsync(s->im[IM_B_BITS].p, 0, 4 * words + 16, c->stream));
     HIPCHK(c, hipMemsetAsync(s->im[IM_B_CTR].p, 0, 8 * IM_C_COUNT, c->stream));
@@ -199,7 +216,7 @@ static int im_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, c
     if (bad && n_e) HIPCHK(c, hipMemcpyAsync(s->im[IM_B_BAD].p, bad, n_e, hipMemcpyHostToDevice, c->stream));
     if (n_roots) HIPCHK(c, hipMemcpyAsync(d_roots, roots, 32 * n_roots, hipMemcpyHostToDevice, c->stream));
 
-    ImMark w;
+    ImMark& w = wd.w;
     w.loc = rs_locator(s);
     w.pf = P<PrPackfile>(s->im[IM_B_PF]);
     w.bad = bad ? P<uint8_t>(s->im[IM_B_BAD]) : nullptr;
@@ -208,21 +225,24 @@ static int im_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, c
     w.errs = P<bw_prune_error>(s->im[IM_B_ERR]);
     w.err_cap = dev_cap;
     w.edges = P<ImEdge>(s->im[IM_B_EDGES]);
+    w.leaf = leaf ? P<ImEdge>(*leaf) : nullptr;
     w.edge_cap = 0;
     int cur = 0;
     w.next = P<uint64_t>(s->im[IM_B_FRONT0 + cur]);
-    if (n_roots) hipLaunchKernelGGL(k_im_roots, wk_grid(n_roots), dim3(256), 0, c->stream, w, d_roots, n_roots);
+    if (n_roots) hipLaunchKernelGGL(k_im_roots<Pol>, wk_grid(n_roots), dim3(256), 0, c->stream, w, d_roots, n_roots);
     HIPCHK(c, hipGetLastError());
 
-    std::vector<bw_prune_error> herr;  // what the chain refused: the host knows it first
+    std::vector<bw_prune_error>& herr = wd.herr;
+    herr.clear();
     std::vector<uint64_t> fr, eidx;
     std::vector<uint8_t> bst;
     std::vector<uint32_t> cst;
     std::vector<uint64_t> slot_at, blen;
-    ImLevels levels;
-    uint64_t ctr[IM_C_COUNT];
+    ImLevels& levels = wd.levels;
+    levels = ImLevels();
+    uint64_t* ctr = wd.ctr;
     uint64_t edge_ub = 0;  // no more edges than this can have been appended
-    HIPCHK(c, hipMemcpyAsync(ctr, w.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ctr, w.ctr, sizeof(wd.ctr), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint64_t n_front = ctr[IM_C_NEXT];
     while (n_front) {
@@ -255,26 +275,64 @@ static int im_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, c
             uint32_t* d_cst = (uint32_t*)t.dst_off;
             HIPCHK(c, hipMemcpyAsync(d_cst, cst.data(), 4 * m, hipMemcpyHostToDevice, c->stream));
             if (int rc = rs_tree_parse(s, t, m, nullptr)) return rc;  // the headers stay in s->q, sized above
-            // the edge list grows by what this sub-batch can append at most, and keeps what it holds
+            // the edge lists grow by what this sub-batch can append at most, and keep what they hold
             const uint64_t more = im_edge_bound(bst.data(), blen.data(), m);
             if (int rc = wk_grow(c, "impact", s->im[IM_B_EDGES], sizeof(ImEdge) * (edge_ub + more) + 16, sizeof(ImEdge) * edge_ub))
                 return rc;
+            if (leaf)
+                if (int rc = wk_grow(c, "impact", *leaf, sizeof(ImEdge) * (edge_ub + more) + 16, sizeof(ImEdge) * edge_ub)) return rc;
             edge_ub += more;
             w.edges = P<ImEdge>(s->im[IM_B_EDGES]);
+            w.leaf = leaf ? P<ImEdge>(*leaf) : nullptr;
             w.edge_cap = edge_ub;
-            hipLaunchKernelGGL(k_im_expand, dim3((uint32_t)m, IM_EXPAND_Y), dim3(256), 0, c->stream, w, d_front + lo,
+            hipLaunchKernelGGL(k_im_expand<Pol>, dim3((uint32_t)m, IM_EXPAND_Y), dim3(256), 0, c->stream, w, d_front + lo,
                                P<uint8_t>(s->slot_buf), t.slot_off, P<RsTreeHdr>(s->q), d_cst, m);
             HIPCHK(c, hipGetLastError());
             // the slots and the tables are reused by the next sub-batch
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         cur ^= 1;
-        HIPCHK(c, hipMemcpyAsync(ctr, w.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ctr, w.ctr, sizeof(wd.ctr), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         n_front = ctr[IM_C_NEXT];
-        if (ctr[IM_C_DROPPED] || ctr[IM_C_EDGES] > edge_ub || !levels.close(ctr[IM_C_EDGES]))
+        if (ctr[IM_C_DROPPED] || ctr[IM_C_EDGES] + ctr[IM_C_LEAF] > edge_ub || !levels.close(ctr[IM_C_EDGES]))
             return im_refuse(c, "an edge count that cannot be");
     }
+    return BW_OK;
+}
+template int bw::im_walk<ImTaint>(bw_restore*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, uint64_t, uint64_t, DevBuf*, ImWalked&);
+template int bw::im_walk<RtReach>(bw_restore*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, uint64_t, uint64_t, DevBuf*, ImWalked&);
+
+int bw::im_errors_out(bw_restore* s, const ImWalked& wd, const char* walk, bw_prune_error* errs, uint64_t err_cap, uint64_t dev_cap,
+                      uint64_t* n_dev_out, uint64_t* n_errors) {
+    bw_ctx* c = s->c;
+    const uint64_t n_dev = wd.ctr[IM_C_ERRORS], dev_take = std::min(n_dev, dev_cap);
+    *n_dev_out = n_dev;
+    if (dev_take) HIPCHK(c, hipMemcpy(errs, s->im[IM_B_ERR].p, dev_take * sizeof(bw_prune_error), hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < wd.herr.size() && dev_take + k < err_cap; k++) errs[dev_take + k] = wd.herr[k];
+    *n_errors = n_dev + wd.herr.size();
+    if (*n_errors > err_cap) {
+        c->err = std::string(walk) + ": " + std::to_string(*n_errors) + " errors do not fit err_cap";
+        return BW_ENOSPC;
+    }
+    return BW_OK;
+}
+
+// Impact's half of the mark: the walk, BELOW to its fixed point over the edges, the results.  *n_dev_out =
+// the errors the kernels met.
+static int im_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, const uint8_t* bad, uint32_t flags,
+                        uint8_t* taint, uint8_t* root_affected, bw_impact_counts* counts, bw_prune_error* errs,
+                        uint64_t err_cap, uint64_t dev_cap, uint64_t* n_dev_out) {
+    const uint64_t n_e = s->entries.size();
+    bw_ctx* c = s->c;
+    memset(counts, 0, sizeof(*counts));
+    // the results: [taint | root_affected]
+    const uint64_t ra_at = (n_e + 15) & ~15ull, out_bytes = ra_at + ((n_roots + 15) & ~15ull);
+    ImWalked wd;
+    if (int rc = im_walk<ImTaint>(s, roots, n_roots, bad, flags, dev_cap, out_bytes, nullptr, wd)) return rc;
+    const ImMark& w = wd.w;
+    const ImLevels& levels = wd.levels;
+    uint8_t *d_taint = wd.d_out, *d_ra = d_taint + ra_at, *d_roots = wd.d_roots;
 
     // BELOW to its least fixed point: sweeps, latest level first, until one changes nothing
     uint64_t n_sweeps = 0, changed = 1;
@@ -299,22 +357,13 @@ static int im_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, c
     if (n_e) HIPCHK(c, hipMemcpyAsync(taint, d_taint, n_e, hipMemcpyDeviceToHost, c->stream));
     if (n_roots) HIPCHK(c, hipMemcpyAsync(root_affected, d_ra, n_roots, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint64_t n_dev = ctr[IM_C_ERRORS], dev_take = std::min(n_dev, dev_cap);
-    *n_dev_out = n_dev;
-    if (dev_take) HIPCHK(c, hipMemcpy(errs, s->im[IM_B_ERR].p, dev_take * sizeof(bw_prune_error), hipMemcpyDeviceToHost));
-    for (uint64_t k = 0; k < herr.size() && dev_take + k < err_cap; k++) errs[dev_take + k] = herr[k];
-    counts->n_trees_expanded = ctr[IM_C_EXPANDED];
+    counts->n_trees_expanded = wd.ctr[IM_C_EXPANDED];
     counts->n_levels = levels.n_levels();
     counts->n_edges = levels.n_edges();
     counts->n_sweeps = n_sweeps;
     for (uint64_t e = 0; e < n_e; e++) counts->n_tainted += taint[e] != 0;
     for (uint64_t r = 0; r < n_roots; r++) counts->n_roots_affected += root_affected[r];
-    counts->n_errors = n_dev + herr.size();
-    if (counts->n_errors > err_cap) {
-        c->err = "impact: " + std::to_string(counts->n_errors) + " errors do not fit err_cap";
-        return BW_ENOSPC;
-    }
-    return BW_OK;
+    return im_errors_out(s, wd, "impact", errs, err_cap, dev_cap, n_dev_out, &counts->n_errors);
 }
 
 extern "C" int bw_impact_mark(bw_restore* s, const uint8_t* roots, uint64_t n_roots, const uint8_t* bad, uint32_t flags,

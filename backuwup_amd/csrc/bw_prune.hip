@@ -162,7 +162,8 @@ static void pr_host_error(std::vector<bw_prune_error>& v, const uint8_t* hash, u
 }
 
 // One walk with a device error list of dev_cap <= err_cap records; *n_dev = the errors the kernels met.
-// im_mark_once (bw_impact.hip) is this loop's twin with a taint beside the live bit: a fix to either belongs in both.
+// im_walk (bw_impact.hip) is this loop's twin with a taint beside the live bit and an edge list, shared by impact and
+// retain: a fix to either belongs in both.
 static int pr_mark_once(bw_restore* s, const uint8_t* roots, uint64_t n_roots, uint32_t flags, uint8_t* live,
                         bw_prune_packfile_stat* stats, bw_prune_counts* counts, bw_prune_error* errs, uint64_t err_cap,
                         uint64_t dev_cap, uint64_t* n_dev_out) {

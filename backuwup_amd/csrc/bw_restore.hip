@@ -340,6 +340,7 @@ extern "C" int bw_restore_close(bw_restore* s) {
     for (auto* walk : {&s->wk, &s->df, &s->pm})
         for (DevBuf& b : *walk) free_dev(b);
     for (DevBuf& b : s->im) free_dev(b);
+    for (DevBuf& b : s->rt) free_dev(b);
     delete s;
     return BW_OK;
 }

@@ -870,6 +870,101 @@ private:
     const std::vector<bw_unpack_entry>& entries_;
 };
 
+// ------------------------------------------------------------------ retain (no counterpart in the reference)
+// Over an open Restore: mark() = for every header entry the set of roots that reach it, from one walk over
+// all roots, with what each root reaches and what it alone holds; drop() = what forgetting each of some
+// sets of roots frees: the live vector and the per-packfile sums a prune mark over the kept roots would
+// give, ready for bw_prune_plan.  Errors are collected and never end a call.
+class Retain {
+public:
+    struct Mark {
+        uint64_t n_roots = 0, words = 1;  // W: the u64 words of one root set
+        std::vector<uint64_t> masks;      // n_entries x W, entry-major: bit r % 64 of word r / 64 = root r
+        std::vector<uint8_t> damaged;     // one byte per header entry
+        std::vector<bw_retain_root> per_root;
+        bw_retain_counts counts{};
+        std::vector<bw_prune_error> errors;  // in no particular order
+
+        bool reaches(uint64_t root, uint64_t entry) const { return masks[entry * words + root / 64] >> (root % 64) & 1; }
+        // a snapshot whose figures are exact, not lower bounds
+        bool complete(uint64_t root) const { return per_root[root].status == 0 && per_root[root].n_damaged == 0; }
+    };
+    struct Drop {
+        std::vector<uint8_t> live;                  // n_sets x n_entries
+        std::vector<bw_prune_packfile_stat> stats;  // n_sets x n_packfiles
+        std::vector<bw_retain_freed> freed;         // one per set
+    };
+
+    Retain(Context& ctx, Restore& session, const std::vector<bw_unpack_entry>& entries, uint64_t n_packfiles)
+        : ctx_(ctx), s_(session), entries_(entries), n_pf_(n_packfiles) {}
+
+    static uint64_t words(uint64_t n_roots) { return n_roots ? (n_roots + 63) / 64 : 1; }
+
+    // the words of the set of these root indices
+    static std::vector<uint64_t> mask_of(const std::vector<uint64_t>& indices, uint64_t n_roots) {
+        std::vector<uint64_t> out(words(n_roots), 0);
+        for (uint64_t r : indices) {
+            if (r >= n_roots) throw Error(BW_EINVAL, "retain: a root index past the roots given");
+            out[r / 64] |= 1ull << (r % 64);
+        }
+        return out;
+    }
+
+    Mark mark(const std::vector<BlobHash>& roots, bool verify = false) {
+        Mark m;
+        m.n_roots = roots.size();
+        m.words = words(roots.size());
+        m.masks.resize(entries_.size() * m.words + 1);
+        m.damaged.resize(entries_.size() + 1);
+        m.per_root.resize(roots.size() + 1);
+        std::vector<uint8_t> flat(32 * roots.size() + 1);
+        for (size_t i = 0; i < roots.size(); i++) std::copy(roots[i].begin(), roots[i].end(), flat.begin() + 32 * i);
+        uint64_t ecap = 64;
+        for (;;) {
+            m.errors.resize(ecap + 1);
+            const int rc = bw_retain_mark(s_.get(), flat.data(), roots.size(), verify ? BW_UNPACK_VERIFY : 0, m.masks.data(),
+                                          m.damaged.data(), m.per_root.data(), &m.counts, m.errors.data(), ecap);
+            if (rc != BW_ENOSPC) {
+                check(rc, ctx_.get());
+                break;
+            }
+            ecap = m.counts.n_errors;
+        }
+        m.masks.resize(entries_.size() * m.words);
+        m.damaged.resize(entries_.size());
+        m.per_root.resize(roots.size());
+        m.errors.resize(m.counts.n_errors);
+        return m;
+    }
+
+    // sets: one list of root indices per question
+    Drop drop(const Mark& m, const std::vector<std::vector<uint64_t>>& sets) {
+        Drop d;
+        std::vector<uint64_t> words;
+        for (const auto& set : sets) {
+            const std::vector<uint64_t> w = mask_of(set, m.n_roots);
+            words.insert(words.end(), w.begin(), w.end());
+        }
+        words.push_back(0);
+        d.live.resize(sets.size() * entries_.size() + 1);
+        d.stats.resize(sets.size() * n_pf_ + 1);
+        d.freed.resize(sets.size() + 1);
+        check(bw_retain_drop(s_.get(), m.masks.data(), m.n_roots, words.data(), sets.size(), d.live.data(), d.stats.data(),
+                             d.freed.data()),
+              ctx_.get());
+        d.live.resize(sets.size() * entries_.size());
+        d.stats.resize(sets.size() * n_pf_);
+        d.freed.resize(sets.size());
+        return d;
+    }
+
+private:
+    Context& ctx_;
+    Restore& s_;
+    const std::vector<bw_unpack_entry>& entries_;
+    uint64_t n_pf_;
+};
+
 // ------------------------------------------------------------------ check (no counterpart in the reference)
 // Over an open Restore: structure() = headers against index items and the layout of every blob
 // section, data() = every selected entry's bytes (BW_CHECK_AUTH: tags only, BW_CHECK_FULL: the unpack

@@ -691,6 +691,63 @@ int bw_impact_paths(bw_restore* session, const uint8_t* roots, uint64_t n_roots,
                     bw_impact_record* records, uint64_t record_cap, uint8_t* names, uint64_t names_cap,
                     bw_impact_root* per_root, bw_impact_paths_counts* counts, bw_prune_error* errs, uint64_t err_cap);
 
+/* ---- retain: which snapshots keep each blob alive, what forgetting a set of them frees ----
+ * The reference cannot ask this; restic answers it with stats and forget --dry-run, borg with its
+ * "deduplicated size" column.  Two steps over an open restore session, both synchronous: bw_retain_mark
+ * walks all roots at once (each distinct tree blob is opened once, as in bw_prune_mark) and gives every
+ * entry the set of roots that reach it; bw_retain_drop answers "what if these roots are forgotten" from
+ * those sets alone, with no tree read, in the form bw_prune_plan takes. */
+#define BW_RETAIN_MAX_ROOTS 4096u
+typedef struct bw_retain_root {
+    uint64_t reached_blobs, reached_bytes;   /* bytes: 12 + length per entry, prune's convention */
+    uint64_t unique_blobs, unique_bytes;     /* entries whose mask is this root's bit alone      */
+    uint64_t n_damaged;                      /* damaged entries with this root in their mask     */
+    uint32_t status, pad;                    /* 0, or why the root itself could not be walked    */
+} bw_retain_root;
+typedef struct bw_retain_counts {
+    uint64_t n_trees_expanded, n_levels, n_edges, n_sweeps, n_errors;
+    uint64_t reached_blobs, reached_bytes, orphan_blobs, orphan_bytes; /* mask != 0 / mask == 0 */
+} bw_retain_counts;
+typedef struct bw_retain_freed {
+    uint64_t freed_blobs, freed_bytes;   /* mask != 0 and every root of it dropped */
+    uint64_t live_blobs, live_bytes;     /* some root of the mask kept             */
+} bw_retain_freed;
+
+/* W = max(1, ceil(n_roots / 64)).  masks (host, n_entries * W words, entry-major): bit r % 64 of
+ * masks[e * W + r / 64] says that root r reaches entry e, which is: bw_prune_mark over the single root r
+ * sets live[e].  Bits at or past n_roots are zero.  Two equal roots each have their own bit.
+ *   The walk is bw_prune_mark's with its rules.  A Tree entry is opened for root r only when r reaches
+ * it through a tree reference (a root, a Dir's child row, a next_sibling); a File row that names a Tree
+ * entry reaches it and does not open it.  So two sets are kept per entry, reach and open: root i seeds
+ * bit i into both sets of the entry it locates to (into reach alone when that is a FileChunk entry);
+ * for every reference of an expanded entry p that locates to c, reach(c) |= open(p), and when it is a
+ * tree reference and c a Tree entry also open(c) |= open(p); the sets are the least fixed point of that
+ * rule.  The expand kernel appends an 8-byte edge per located reference, a propagate kernel sweeps the
+ * edges between Tree entries earliest level first until a sweep changes nothing (n_sweeps, >= 1), and
+ * the other edges are settled in one pass after that.  n_edges counts both kinds.
+ *   damaged[e] (host, one byte per entry) is nonzero when e is a reached FileChunk entry whose range
+ * fails prune's range rule, or a queued Tree entry that could not be expanded (BW_UNPACK_ERANGE / _ETAG
+ * / _EZSTD / _EDIGEST, BW_RESTORE_EFORMAT), or an expanded Tree entry that holds a reference that does
+ * not locate or a tree reference to a FileChunk entry.  per_root[r].status is the locate status of root
+ * r's own reference, or BW_RESTORE_ENOTTREE, else 0.  A snapshot is complete when status == 0 and
+ * n_damaged == 0; otherwise what lies below the damage was not seen and its figures are lower bounds.
+ *   Errors are bw_prune_mark's records, the same multiset as bw_prune_mark over the same roots, and
+ * never stop the walk; counts->n_errors > err_cap -> BW_ENOSPC with everything else filled.  flags:
+ * BW_UNPACK_VERIFY or 0.  n_roots > BW_RETAIN_MAX_ROOTS, or a session of 2^31 entries or more ->
+ * BW_ENOMEM.  With no roots every mask is zero and every entry an orphan. */
+int bw_retain_mark(bw_restore* session, const uint8_t* roots, uint64_t n_roots, uint32_t flags,
+                   uint64_t* masks, uint8_t* damaged, bw_retain_root* per_root, bw_retain_counts* counts,
+                   bw_prune_error* errs, uint64_t err_cap);
+
+/* masks: as bw_retain_mark returned them for n_roots roots.  drop (host, n_sets * W words): one root set
+ * per question.  live (host, n_sets * n_entries bytes, or NULL): live[q * n_entries + e] = 1 when
+ * masks[e] & ~drop[q] is nonzero.  stats (host, n_sets * n_packfiles records, or NULL): bw_prune_mark's
+ * per-packfile sums for that live vector.  freed: n_sets records.  For a sound store live and stats are
+ * what bw_prune_mark over the kept roots returns, and go straight into bw_prune_plan.  A mask or drop
+ * word with a bit at or past n_roots -> BW_EINVAL; n_roots > BW_RETAIN_MAX_ROOTS -> BW_ENOMEM. */
+int bw_retain_drop(bw_restore* session, const uint64_t* masks, uint64_t n_roots, const uint64_t* drop,
+                   uint64_t n_sets, uint8_t* live, bw_prune_packfile_stat* stats, bw_retain_freed* freed);
+
 /* ---- check: is this store sound, are these bytes still the bytes that were sealed ----
  * The reference never verifies what it has written; this goes past it as prune does.  Three layers,
  * all synchronous: bw_auth(_device) recomputes AES-GCM tags without decrypting, bw_check_structure

@@ -347,6 +347,45 @@ pub mod ffi {
         pub n_errors: u64,
     }
 
+    pub const BW_RETAIN_MAX_ROOTS: u64 = 4096;
+
+    /// What one root of `bw_retain_mark` reaches, what it alone holds, and whether it could be walked.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_retain_root {
+        pub reached_blobs: u64,
+        pub reached_bytes: u64,
+        pub unique_blobs: u64,
+        pub unique_bytes: u64,
+        pub n_damaged: u64,
+        pub status: u32,
+        pub pad: u32,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_retain_counts {
+        pub n_trees_expanded: u64,
+        pub n_levels: u64,
+        pub n_edges: u64,
+        pub n_sweeps: u64,
+        pub n_errors: u64,
+        pub reached_blobs: u64,
+        pub reached_bytes: u64,
+        pub orphan_blobs: u64,
+        pub orphan_bytes: u64,
+    }
+
+    /// What one drop set of `bw_retain_drop` frees and keeps.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_retain_freed {
+        pub freed_blobs: u64,
+        pub freed_bytes: u64,
+        pub live_blobs: u64,
+        pub live_bytes: u64,
+    }
+
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default)]
     pub struct bw_check_packfile_stat {
@@ -639,6 +678,12 @@ pub mod ffi {
                                records: *mut bw_impact_record, record_cap: u64, names: *mut u8, names_cap: u64,
                                per_root: *mut bw_impact_root, counts: *mut bw_impact_paths_counts,
                                errs: *mut bw_prune_error, err_cap: u64) -> c_int;
+
+        pub fn bw_retain_mark(session: *mut bw_restore, roots: *const u8, n_roots: u64, flags: u32, masks: *mut u64,
+                              damaged: *mut u8, per_root: *mut bw_retain_root, counts: *mut bw_retain_counts,
+                              errs: *mut bw_prune_error, err_cap: u64) -> c_int;
+        pub fn bw_retain_drop(session: *mut bw_restore, masks: *const u64, n_roots: u64, drop: *const u64, n_sets: u64,
+                              live: *mut u8, stats: *mut bw_prune_packfile_stat, freed: *mut bw_retain_freed) -> c_int;
 
         pub fn bw_auth_device(ctx: *mut bw_ctx, prk: *const u8, d_src: *const u8, src_off: *const u64,
                               src_len: *const u64, n: u64, info: *const u8, info_len: u32, nonces: *const u8,

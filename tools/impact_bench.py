@@ -31,18 +31,20 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from unpack_bench import timed  # noqa: E402
 
 
-def main():
-    ap = argparse.ArgumentParser()
+def store_arguments(ap):
     ap.add_argument("--small-files", type=int, default=200000)
     ap.add_argument("--snapshots", type=int, default=8)
     ap.add_argument("--changed", type=float, default=0.01)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--slots", type=int, default=0)
-    args = ap.parse_args()
 
+
+def build_store(args):
+    """The store on the device, shared with tools/retain_bench.py: a dict of ctx, sync, prk, d_pf, ids,
+    entries, items, plan0, roots, nf, ns, n_mod, n_trees."""
     import numpy as np
     import torch
-    from backuwup_amd import Context, _lib, impact, prune, restore
+    from backuwup_amd import Context
     from backuwup_amd.synth import splitmix_torch
 
     dev = torch.device("cuda", 0)
@@ -140,10 +142,26 @@ def main():
     for k, p in enumerate(plan0):
         which[int(p["first_blob"]):int(p["first_blob"] + p["n_blobs"])] = k
     items = np.concatenate([digests, ids[which]], axis=1)
+    return dict(ctx=ctx, sync=sync, prk=prk, d_pf=d_pf, ids=ids, entries=entries, items=items, plan0=plan0, roots=roots, nf=nf,
+                ns=ns, n_mod=n_mod, n_trees=n_trees)
 
-    def ms(ts):
-        g = sorted(t * 1e3 for t in ts)
-        return {"ms_median": round(g[len(g) // 2], 2), "ms_min": round(g[0], 2), "ms_max": round(g[-1], 2), "reps": len(ts)}
+
+def ms(ts):
+    g = sorted(t * 1e3 for t in ts)
+    return {"ms_median": round(g[len(g) // 2], 2), "ms_min": round(g[0], 2), "ms_max": round(g[-1], 2), "reps": len(ts)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    store_arguments(ap)
+    args = ap.parse_args()
+
+    import numpy as np
+    from backuwup_amd import _lib, impact, prune, restore
+    st = build_store(args)
+    ctx, sync, prk, d_pf, ids, entries, items, plan0, roots = (st[k] for k in ("ctx", "sync", "prk", "d_pf", "ids", "entries", "items",
+                                                                                 "plan0", "roots"))
+    nf, ns, n_mod, n_trees = st["nf"], st["ns"], st["n_mod"], st["n_trees"]
 
     out = {"commit": os.environ.get("BW_COMMIT"), "files": nf, "snapshots": ns, "changed_per_snapshot": n_mod,
            "tree_blobs": n_trees, "entries": int(len(entries)), "packfiles": int(len(plan0)), "slots": args.slots or 1024}
