@@ -1,6 +1,7 @@
 // The host arithmetic of retain (backuwup_amd/csrc/bw_retain_host.h) in a stand-alone program: the words
 // of a root set, where a root's bit lies, the bits that name a root, the refusal of a foreign bit, the
-// drop predicate and the forward order of a sweep.  Every expected value is worked out by hand
+// drop predicate, the forward order of a sweep, and the last word's valid bits at 63, 64, 65, 4095 and 4096
+// roots with a foreign bit planted in the last row.  Every expected value is worked out by hand
 // (tests/test_retain_host.py holds the output); built plain and under the address and undefined sanitizers.
 #include <cstdio>
 #include <vector>
@@ -43,6 +44,24 @@ int main() {
         L.close(5), L.close(5), L.close(12), L.close(13);
         for (const auto& r : rt_sweep(L)) std::printf("F range %llu %llu\n", (unsigned long long)r.first, (unsigned long long)r.second);
         std::printf("F backward first %llu\n", (unsigned long long)L.sweep().front().first);
+    }
+    {   // G: the last word at the edges of a word and of the limit.  Three rows with every valid bit set are clean;
+        // then one bit in the last word of the last row: its top bit, and its lowest bit no root has (bit 0 where
+        // the word is full).  Past the last word nothing is valid.
+        const uint64_t ns[5] = {63, 64, 65, RT_MAX_ROOTS - 1, RT_MAX_ROOTS};
+        for (uint64_t n : ns) {
+            const uint64_t W = rt_words(n), last = rt_valid(n, W - 1);
+            std::vector<uint64_t> rows(3 * W);
+            for (uint64_t i = 0; i < 3; i++)
+                for (uint64_t w = 0; w < W; w++) rows[i * W + w] = rt_valid(n, w);
+            const long long clean = (long long)rt_foreign(rows.data(), 3, W, n);
+            std::vector<uint64_t> top = rows, low = rows;
+            top[3 * W - 1] |= 1ull << 63;
+            low[3 * W - 1] |= last + 1 ? last + 1 : 1;
+            std::printf("G %llu %llu %llx %llx %lld %lld %lld\n", (unsigned long long)n, (unsigned long long)W, (unsigned long long)last,
+                        (unsigned long long)rt_valid(n, W), clean, (long long)rt_foreign(top.data(), 3, W, n),
+                        (long long)rt_foreign(low.data(), 3, W, n));
+        }
     }
     return 0;
 }
