@@ -205,6 +205,36 @@ class BwRetainFreed(ctypes.Structure):
                 ("live_bytes", ctypes.c_uint64)]
 
 
+BW_FIND_MAX_PATTERNS = 32
+BW_FIND_ICASE, BW_FIND_SUBTREE, BW_FIND_CHUNKS = 2, 4, 8
+BW_FIND_HIT, BW_FIND_UNREADABLE, BW_FIND_TRUNCATED, BW_FIND_CYCLIC, BW_FIND_PRUNED = 1, 2, 4, 8, 16
+
+
+class BwFindQuery(ctypes.Structure):
+    _fields_ = [("patterns", ctypes.c_void_p), ("pattern_off", ctypes.c_void_p), ("n_patterns", ctypes.c_uint32),
+                ("kinds", ctypes.c_uint32), ("size_min", ctypes.c_uint64), ("size_max", ctypes.c_uint64),
+                ("mtime_min", ctypes.c_uint64), ("mtime_max", ctypes.c_uint64)]
+
+
+class BwFindRecord(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("root", ctypes.c_uint64), ("parent", ctypes.c_uint64),
+                ("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint64), ("kind", ctypes.c_uint32),
+                ("meta_flags", ctypes.c_uint32), ("size", ctypes.c_uint64), ("mtime", ctypes.c_uint64),
+                ("ctime", ctypes.c_uint64), ("child_first", ctypes.c_uint64), ("n_children", ctypes.c_uint64),
+                ("patterns", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class BwFindRoot(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_uint64), ("n_hits", ctypes.c_uint64), ("n_hit_files", ctypes.c_uint64),
+                ("hit_bytes", ctypes.c_uint64), ("n_unreadable", ctypes.c_uint64)]
+
+
+class BwFindCounts(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_uint64), ("name_bytes", ctypes.c_uint64), ("n_chunks", ctypes.c_uint64),
+                ("n_levels", ctypes.c_uint64), ("n_opened", ctypes.c_uint64), ("n_pruned", ctypes.c_uint64),
+                ("n_errors", ctypes.c_uint64)]
+
+
 BW_CHECK_E_RANGE, BW_CHECK_E_ORDER, BW_CHECK_E_UNINDEXED, BW_CHECK_E_SHADOWED = 1, 2, 4, 8
 BW_CHECK_SKIPPED, BW_CHECK_IDUPLICATE = 32, 33
 BW_CHECK_AUTH, BW_CHECK_FULL = 1, 2
@@ -381,6 +411,10 @@ SIGNATURES = [
                                       ctypes.POINTER(BwRetainCounts), ctypes.POINTER(BwPruneError), ctypes.c_uint64]),
     ("bw_retain_drop", ctypes.c_int, [vp, u64p, ctypes.c_uint64, u64p, ctypes.c_uint64, u8p,
                                       ctypes.POINTER(BwPrunePackfileStat), ctypes.POINTER(BwRetainFreed)]),
+    ("bw_find_paths", ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.POINTER(BwFindQuery), ctypes.c_uint32,
+                                     ctypes.POINTER(BwFindRecord), ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint64,
+                                     ctypes.POINTER(BwFindRoot), ctypes.POINTER(BwFindCounts), ctypes.POINTER(BwPruneError),
+                                     ctypes.c_uint64]),
     ("bw_auth_device", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_auth", ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64, vp, ctypes.c_uint32, vp, u8p]),
     ("bw_check_structure", ctypes.c_int, [vp, u8p, u8p, ctypes.POINTER(BwCheckPackfileStat),

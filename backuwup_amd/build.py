@@ -17,7 +17,7 @@ LIB_DEBUG = os.path.join(HERE, "libbackuwup_amd_debug.so")
 SOURCES = ["bw_capi.hip", "bw_cdc.hip", "bw_blake3.hip", "bw_dedup.hip", "bw_comm.hip", "bw_tree.hip", "bw_seal.hip",
            "bw_pack.hip", "bw_zstd.hip", "bw_dropin.hip", "bw_stream.hip", "bw_capi_pack.hip", "bw_b3_small.hip", "bw_zstd_dec.hip",
            "bw_restore.hip", "bw_prune.hip", "bw_check.hip", "bw_rekey.hip", "bw_parity.hip", "bw_diff.hip", "bw_parent.hip", "bw_impact.hip",
-           "bw_retain.hip"]
+           "bw_retain.hip", "bw_find.hip"]
 HEADERS = ["backuwup_gpu.h", "backuwup_gpu_pack.h"]  # include/
 ROCM_LIB = "/opt/rocm/lib"
 ARCH = os.environ.get("BW_OFFLOAD_ARCH", "gfx950")
@@ -30,13 +30,14 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # hashing (bw_b3_small.hip) are outside the digest too, as is the read side (bw_zstd_dec.hip and its headers, and
 # the restore session, bw_restore.hip, and prune and check over it, bw_prune.hip, bw_check.hip; parity,
 # bw_parity.hip; the store's host-only layout rules, bw_store_layout.h; the diff walk, bw_diff.hip; the parent match, bw_parent.hip;
-# the tree-chain fetch those two share, bw_walk.h and its host-only planner bw_walk_host.h; impact, bw_impact.hip; retain, bw_retain.hip)
+# the tree-chain fetch those two share, bw_walk.h and its host-only planner bw_walk_host.h; impact, bw_impact.hip; retain, bw_retain.hip; find, bw_find.hip and its host-only pattern compiler bw_find_host.h)
 OFF_PATH = ("bw_zstd.hip", "bw_seal.hip", "bw_pack.hip", "bw_tree.hip", "bw_comm.hip", "bw_dropin.hip", "bw_stream.hip",
             "bw_capi_pack.hip", "bw_b3_small.hip", "bw_b3_small.h", "bw_zstd_dec.hip", "bw_zstd_dec_core.h",
             "bw_unpack.h", "bw_restore.hip", "bw_restore.h", "bw_prune.hip", "bw_prune.h", "bw_check.hip", "bw_check.h", "bw_seal.h",
             "bw_rekey.hip", "bw_parity.hip", "bw_store_layout.h", "bw_diff.hip", "bw_diff.h", "bw_diff_host.h",
             "bw_parent.hip", "bw_parent.h", "bw_parent_host.h", "bw_walk.h", "bw_walk_host.h",
-            "bw_impact.hip", "bw_impact.h", "bw_impact_host.h", "bw_retain.hip", "bw_retain.h", "bw_retain_host.h")
+            "bw_impact.hip", "bw_impact.h", "bw_impact_host.h", "bw_retain.hip", "bw_retain.h", "bw_retain_host.h",
+            "bw_find.hip", "bw_find.h", "bw_find_host.h")
 
 
 def _code_only(text):

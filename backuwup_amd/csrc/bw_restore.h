@@ -252,4 +252,5 @@ struct bw_restore {
     DevBuf pm[12];  // parent match (bw_parent.hip): its own buffers by PM_B_*
     DevBuf im[16];  // impact (bw_impact.hip): the mark's and the report walk's buffers by IM_B_*
     DevBuf rt[8];   // retain (bw_retain.hip): its own buffers by RT_B_*; its walk's are impact's mark's
+    DevBuf fd[16];  // find (bw_find.hip): its own buffers by FD_B_*
 };

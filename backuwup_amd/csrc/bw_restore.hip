@@ -341,6 +341,7 @@ extern "C" int bw_restore_close(bw_restore* s) {
         for (DevBuf& b : *walk) free_dev(b);
     for (DevBuf& b : s->im) free_dev(b);
     for (DevBuf& b : s->rt) free_dev(b);
+    for (DevBuf& b : s->fd) free_dev(b);
     delete s;
     return BW_OK;
 }

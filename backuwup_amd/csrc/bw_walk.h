@@ -252,6 +252,7 @@ struct WkHost {
     uint64_t n_e;
     typename Pol::Walk w;
     uint64_t err_ub = 0;  // no more errors than this can have been written
+    uint64_t n_opened = 0;  // the blobs handed to the unpack chain so far (find reports it)
     WkLevel lv;
     std::vector<WkOwner> owners;  // of the level's chains
     // scratch
@@ -334,6 +335,7 @@ static int wk_fetch(WkHost<Pol>& H, const WkRef* d_refs, uint64_t n_refs, bool h
             for (uint64_t k = 0; k < m; k++) H.eidx[k] = (uint32_t)H.out[H.located[lo + k]];
             RsTables t;
             if (int rc = rs_tree_decode(s, H.eidx, H.flags, m, t, H.bst)) return rc;
+            H.n_opened += m;
             if (int rc = rs_tree_parse(s, t, m, &H.hd)) return rc;
             HIPCHK(c, hipStreamSynchronize(c->stream));
             H.take.resize(m);

@@ -870,6 +870,92 @@ private:
     const std::vector<bw_unpack_entry>& entries_;
 };
 
+// ------------------------------------------------------------------ find (no counterpart in the reference)
+// Over an open Restore: paths() = the records of every item the walk looked at under each root, the hits
+// flagged, for up to BW_FIND_MAX_PATTERNS glob patterns; a directory no pattern can match below is not
+// opened.  Errors are collected and never end a call.
+class Find {
+public:
+    struct Query {
+        std::vector<std::string> patterns;
+        uint32_t kinds = 0;  // 1u << BW_TREE_FILE, 1u << BW_TREE_DIR; 0 = both
+        uint64_t size_min = 0, size_max = ~0ull, mtime_min = 0, mtime_max = ~0ull;
+    };
+    struct Paths {
+        std::vector<bw_find_record> records;  // a parent before its children
+        std::vector<uint8_t> names;
+        std::vector<uint8_t> chunks;  // 32 bytes a row: the hit files' rows with BW_FIND_CHUNKS
+        std::vector<bw_find_root> per_root;
+        bw_find_counts counts{};
+        std::vector<bw_prune_error> errors;
+
+        std::string name(size_t i) const {
+            const bw_find_record& r = records[i];
+            return std::string(names.begin() + r.name_off, names.begin() + r.name_off + r.name_len);
+        }
+        // the names joined through parent; a root's path is empty, an unreadable item's name is "?"
+        std::string path(size_t i) const {
+            const bw_find_record& r = records[i];
+            const std::string own = (r.flags & BW_FIND_UNREADABLE) ? "?" : name(i);
+            if (r.parent == ~0ull) return (r.flags & BW_FIND_UNREADABLE) ? own : "";
+            const std::string up = path(r.parent);
+            return up.empty() ? own : up + "/" + own;
+        }
+    };
+
+    Find(Context& ctx, Restore& session) : ctx_(ctx), s_(session) {}
+
+    // flags: BW_FIND_ICASE | BW_FIND_SUBTREE | BW_FIND_CHUNKS | BW_UNPACK_VERIFY; the buffers grow until the walk fits them
+    Paths paths(const std::vector<BlobHash>& roots, const Query& q, uint32_t flags = 0) {
+        Paths d;
+        std::vector<uint8_t> flat(32 * roots.size() + 1), bytes(1);
+        for (size_t i = 0; i < roots.size(); i++) std::copy(roots[i].begin(), roots[i].end(), flat.begin() + 32 * i);
+        std::vector<uint64_t> off(1, 0);
+        for (const std::string& p : q.patterns) {
+            bytes.insert(bytes.end() - 1, p.begin(), p.end());
+            off.push_back(bytes.size() - 1);
+        }
+        bw_find_query fq{};
+        fq.patterns = bytes.data();
+        fq.pattern_off = off.data();
+        fq.n_patterns = (uint32_t)q.patterns.size();
+        fq.kinds = q.kinds;
+        fq.size_min = q.size_min;
+        fq.size_max = q.size_max;
+        fq.mtime_min = q.mtime_min;
+        fq.mtime_max = q.mtime_max;
+        uint64_t rcap = 1024, ncap = 1 << 16, ccap = 1024, ecap = 64;
+        for (;;) {
+            d.records.resize(rcap + 1);
+            d.names.resize(ncap + 1);
+            d.chunks.resize(32 * ccap + 1);
+            d.errors.resize(ecap + 1);
+            d.per_root.assign(roots.size() + 1, bw_find_root{});
+            const int rc = bw_find_paths(s_.get(), flat.data(), roots.size(), &fq, flags, d.records.data(), rcap, d.names.data(), ncap,
+                                         d.chunks.data(), ccap, d.per_root.data(), &d.counts, d.errors.data(), ecap);
+            if (rc != BW_ENOSPC) {
+                check(rc, ctx_.get());
+                break;
+            }
+            // the counts are the totals up to the level that did not fit
+            if (d.counts.n_records > rcap) rcap = std::max<uint64_t>(2 * rcap, d.counts.n_records);
+            if (d.counts.name_bytes > ncap) ncap = std::max<uint64_t>(2 * ncap, d.counts.name_bytes);
+            if (d.counts.n_chunks > ccap) ccap = std::max<uint64_t>(2 * ccap, d.counts.n_chunks);
+            if (d.counts.n_errors > ecap) ecap = d.counts.n_errors;
+        }
+        d.records.resize(d.counts.n_records);
+        d.names.resize(d.counts.name_bytes);
+        d.chunks.resize(32 * d.counts.n_chunks);
+        d.errors.resize(d.counts.n_errors);
+        d.per_root.resize(roots.size());
+        return d;
+    }
+
+private:
+    Context& ctx_;
+    Restore& s_;
+};
+
 // ------------------------------------------------------------------ retain (no counterpart in the reference)
 // Over an open Restore: mark() = for every header entry the set of roots that reach it, from one walk over
 // all roots, with what each root reaches and what it alone holds; drop() = what forgetting each of some

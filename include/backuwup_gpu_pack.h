@@ -748,6 +748,95 @@ int bw_retain_mark(bw_restore* session, const uint8_t* roots, uint64_t n_roots, 
 int bw_retain_drop(bw_restore* session, const uint64_t* masks, uint64_t n_roots, const uint64_t* drop,
                    uint64_t n_sets, uint8_t* live, bw_prune_packfile_stat* stats, bw_retain_freed* freed);
 
+/* ---- find: which paths of which snapshots match a set of patterns ----
+ * The reference cannot ask this; restic answers it with find and restore --include.  One synchronous
+ * call over an open restore session: a fourth policy over the tree-chain fetch that the diff walk, the
+ * parent match and impact's report walk share, and a bit-parallel glob automaton whose state is carried
+ * down the path, so that a directory no pattern can match below is never opened.
+ *   A pattern is a valid UTF-8 byte string matched against an item's path: its names from the root's
+ * child down, joined by '/'.  The root itself has the path "" and never matches.  Within a component
+ * '*' matches zero or more bytes other than '/', '?' one code point other than '/', [abc] [a-z] [!a-z]
+ * [^a-z] are classes of ASCII members (a negated class matches one code point that is not in it and is
+ * not '/'), \x is a literal x, any other byte is a literal.  A component that is exactly ** stands for
+ * zero or more whole components.  A leading '/' anchors the pattern at the root's children; without one
+ * it floats, as if it began with a ** component.  A trailing '/' means directories only.  BW_EINVAL with
+ * the reason in bw_last_error: an empty pattern or component (a//b), an unterminated class, a dangling
+ * backslash, invalid UTF-8, a class member that is not ASCII, a '/' inside a class or behind a
+ * backslash, a class range that runs backwards, a pattern that needs more than 64 automaton states (a
+ * state per literal byte, '?', class and run of '*', one per component end, one per run of ** components,
+ * one for floating).  BW_FIND_ICASE folds ASCII letters only. */
+#define BW_FIND_MAX_PATTERNS 32u
+#define BW_FIND_ICASE   2u  /* ASCII case folding */
+#define BW_FIND_SUBTREE 4u  /* everything below a Dir that a pattern matches is matched by that pattern too */
+#define BW_FIND_CHUNKS  8u  /* fetch the chunk rows of the File records that are hits */
+/* BW_UNPACK_VERIFY (1) may be OR-ed in as for the other walks */
+
+#define BW_FIND_HIT        1u
+#define BW_FIND_UNREADABLE 2u  /* first piece unlocatable, not a tree, or refused: hash only, empty name, not matched, not descended */
+#define BW_FIND_TRUNCATED  4u  /* a later piece of its chain is lost: the list ends there */
+#define BW_FIND_CYCLIC     8u  /* its hash is one of its ancestors' on this path: not descended */
+#define BW_FIND_PRUNED    16u  /* a Dir no pattern can match below: its rows were never fetched */
+
+typedef struct bw_find_query {
+    const uint8_t* patterns;     /* the patterns' bytes back to back */
+    const uint64_t* pattern_off; /* n_patterns + 1 offsets */
+    uint32_t n_patterns, kinds;  /* kinds: bit BW_TREE_FILE, bit BW_TREE_DIR (1u << kind); 0 = both */
+    uint64_t size_min, size_max, mtime_min, mtime_max; /* inclusive; 0 .. ~0 = no filter */
+} bw_find_query;
+typedef struct bw_find_record {
+    uint8_t hash[32];
+    uint64_t root, parent;           /* parent: the record of the item above, ~0 for a root; always lower than its own */
+    uint64_t name_off, name_len;     /* into `names`; empty for an unreadable item */
+    uint32_t kind, meta_flags;       /* BW_TREE_FILE / _DIR; BW_TREE_HAS_* */
+    uint64_t size, mtime, ctime;
+    uint64_t child_first, n_children; /* Dir: its rows read and the record of the first (they are consecutive records; 0, 0
+                                         when PRUNED, CYCLIC or empty); File with BW_FIND_CHUNKS and HIT: its rows in `chunks` */
+    uint32_t patterns;                /* the patterns that match its path, inherited ones included */
+    uint32_t flags;                   /* BW_FIND_HIT / _UNREADABLE / _TRUNCATED / _CYCLIC / _PRUNED */
+} bw_find_record;
+typedef struct bw_find_root   { uint64_t n_records, n_hits, n_hit_files, hit_bytes, n_unreadable; } bw_find_root;
+typedef struct bw_find_counts { uint64_t n_records, name_bytes, n_chunks, n_levels, n_opened, n_pruned, n_errors; } bw_find_counts;
+
+/* roots: host, 32 bytes each.  flags: BW_FIND_* and BW_UNPACK_VERIFY.  records, names, chunks (32 bytes a
+ * row), per_root (one per root) and errs are host arrays.
+ *   Levels.  An item is (root index, parent record, tree reference, carried states: one 64-bit state set
+ * per pattern).  Level 0 is every root in root order; a root's record is never a hit and carries no
+ * pattern bit, and its children start from the patterns' initial states.
+ *   Per level only the first piece of every item is opened, for its header and name (the parent match's
+ * second fetch).  The match kernel runs each item's name through every pattern from its parent's carried
+ * states: a pattern bit is set when the state after the name accepts (a trailing '/' requires kind Dir),
+ * and with BW_FIND_SUBTREE also when the parent has it.  HIT is set when patterns != 0 and the kind, size
+ * and mtime filters hold; an item without BW_TREE_HAS_SIZE or BW_TREE_HAS_MTIME fails a filter on that
+ * field that is narrower than 0 .. ~0.  A Dir's carried states are the states after a further '/'.  A
+ * Dir is PRUNED when every carried state is empty and it hands no pattern bit down.  Then the rows of
+ * every Dir item that is not PRUNED, CYCLIC or UNREADABLE are fetched, the whole next_sibling chain in
+ * chain order, and every row becomes an item of the next level, in row order.
+ *   Records.  Every item gives one record, hits, misses and unreadable items alike, in level order and
+ * item order within the level, so every hit's ancestors are records and a path is the parent chain.  A
+ * Dir's children are the records child_first .. child_first + n_children.  The same subtree under two
+ * roots, or twice under one root, gives records under each.
+ *   Chunk rows.  With BW_FIND_CHUNKS the chains of the File records with HIT are fetched after their
+ * level and their rows land in `chunks` in record order; without it no File's rows are read.
+ * chunks_cap > 0 without the flag is allowed and unused.
+ *   Counts.  n_opened counts the tree blobs handed to the unpack chain: one per located first piece,
+ * one per located piece of a chain that is fetched (the first piece again: a fetch decodes what it
+ * opens once, and keeps nothing between fetches).  n_pruned counts the PRUNED records.  per_root sums the
+ * records returned; hit_bytes sums the sizes of hit Files.
+ *   Errors never stop the walk and use prune's record with the diff walk's meaning: a locate status or
+ * BW_RESTORE_ENOTTREE for an item's reference, a chain or parser refusal of a piece, and
+ * BW_RESTORE_EFORMAT for a CYCLIC item or a chain of more pieces than the store has entries.
+ *   Capacity and hard limit are bw_impact_paths' word for word: the walk stops at the first level whose
+ * records, names or chunk rows do not fit and returns BW_ENOSPC with counts holding the totals up to and
+ * including that level; the levels before it are filled in, and nothing is written past a cap; per_root
+ * is partial then.  counts->n_errors > err_cap -> BW_ENOSPC with everything else filled.  A level is
+ * indexed in 32 bits: more than 2^30 items or rows in a level ends the call with BW_ENOMEM.
+ * n_patterns == 0 or > BW_FIND_MAX_PATTERNS, a kinds bit other than the two, or a refused pattern ->
+ * BW_EINVAL. */
+int bw_find_paths(bw_restore* session, const uint8_t* roots, uint64_t n_roots, const bw_find_query* query, uint32_t flags,
+                  bw_find_record* records, uint64_t record_cap, uint8_t* names, uint64_t names_cap,
+                  uint8_t* chunks, uint64_t chunks_cap, bw_find_root* per_root, bw_find_counts* counts,
+                  bw_prune_error* errs, uint64_t err_cap);
+
 /* ---- check: is this store sound, are these bytes still the bytes that were sealed ----
  * The reference never verifies what it has written; this goes past it as prune does.  Three layers,
  * all synchronous: bw_auth(_device) recomputes AES-GCM tags without decrypting, bw_check_structure

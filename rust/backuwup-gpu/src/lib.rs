@@ -347,6 +347,72 @@ pub mod ffi {
         pub n_errors: u64,
     }
 
+    pub const BW_FIND_MAX_PATTERNS: u32 = 32;
+    pub const BW_FIND_ICASE: u32 = 2;
+    pub const BW_FIND_SUBTREE: u32 = 4;
+    pub const BW_FIND_CHUNKS: u32 = 8;
+    pub const BW_FIND_HIT: u32 = 1;
+    pub const BW_FIND_UNREADABLE: u32 = 2;
+    pub const BW_FIND_TRUNCATED: u32 = 4;
+    pub const BW_FIND_CYCLIC: u32 = 8;
+    pub const BW_FIND_PRUNED: u32 = 16;
+
+    /// The question of `bw_find_paths`: glob patterns back to back, and the kind, size and mtime filters.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct bw_find_query {
+        pub patterns: *const u8,
+        pub pattern_off: *const u64,
+        pub n_patterns: u32,
+        pub kinds: u32,
+        pub size_min: u64,
+        pub size_max: u64,
+        pub mtime_min: u64,
+        pub mtime_max: u64,
+    }
+
+    /// One item of `bw_find_paths`: a path under one root, a hit or on the way to one.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_find_record {
+        pub hash: [u8; 32],
+        pub root: u64,
+        pub parent: u64,
+        pub name_off: u64,
+        pub name_len: u64,
+        pub kind: u32,
+        pub meta_flags: u32,
+        pub size: u64,
+        pub mtime: u64,
+        pub ctime: u64,
+        pub child_first: u64,
+        pub n_children: u64,
+        pub patterns: u32,
+        pub flags: u32,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_find_root {
+        pub n_records: u64,
+        pub n_hits: u64,
+        pub n_hit_files: u64,
+        pub hit_bytes: u64,
+        pub n_unreadable: u64,
+    }
+
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct bw_find_counts {
+        pub n_records: u64,
+        pub name_bytes: u64,
+        pub n_chunks: u64,
+        pub n_levels: u64,
+        pub n_opened: u64,
+        pub n_pruned: u64,
+        pub n_errors: u64,
+    }
+
     pub const BW_RETAIN_MAX_ROOTS: u64 = 4096;
 
     /// What one root of `bw_retain_mark` reaches, what it alone holds, and whether it could be walked.
@@ -678,6 +744,11 @@ pub mod ffi {
                                records: *mut bw_impact_record, record_cap: u64, names: *mut u8, names_cap: u64,
                                per_root: *mut bw_impact_root, counts: *mut bw_impact_paths_counts,
                                errs: *mut bw_prune_error, err_cap: u64) -> c_int;
+
+        pub fn bw_find_paths(session: *mut bw_restore, roots: *const u8, n_roots: u64, query: *const bw_find_query, flags: u32,
+                             records: *mut bw_find_record, record_cap: u64, names: *mut u8, names_cap: u64,
+                             chunks: *mut u8, chunks_cap: u64, per_root: *mut bw_find_root, counts: *mut bw_find_counts,
+                             errs: *mut bw_prune_error, err_cap: u64) -> c_int;
 
         pub fn bw_retain_mark(session: *mut bw_restore, roots: *const u8, n_roots: u64, flags: u32, masks: *mut u64,
                               damaged: *mut u8, per_root: *mut bw_retain_root, counts: *mut bw_retain_counts,
